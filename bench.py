@@ -7,6 +7,13 @@ synthetic data with random-init weights. Run directly for N=1 or under
 (reads RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from the env).
 
 Prints ONE JSON line from rank 0 with the whole-job aggregate.
+
+A plain run does only what the headline needs: set up, warm up, time
+`--steps` optimizer steps, print the result line. `--dump-outputs DIR`
+additionally writes what the last timed step produced (see _dump_outputs).
+`--full` is where any measurement beyond the headline belongs (baselines,
+other precisions or sizes, per-kernel figures); the headline is all this
+benchmark measures today, so `--full` currently adds nothing to a plain run.
 """
 from __future__ import annotations
 
@@ -28,6 +35,40 @@ from kubeflow_amd.parallel import dist as kdist  # noqa: E402
 from kubeflow_amd.runtime import Trainer, TrainConfig  # noqa: E402
 
 
+DUMP_SAMPLE = 1 << 20  # elements sampled from each large flat buffer
+
+
+def _dump_outputs(out_dir, trainer, loss):
+    """Write what the last timed step computed as float32 `<name>.npy`:
+    the loss the caller of Trainer.step receives, the pre-clip gradient
+    norm, and a fixed seeded sample of the updated flat parameters and of
+    the gradients that produced them (the full buffers are tens of GB; the
+    sample indices depend only on the buffer size, so two builds run with
+    the same arguments write comparable arrays)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, t):
+        a = t.detach().to(torch.float32).reshape(-1).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+    save("loss", loss)
+    gnorm = getattr(trainer, "last_grad_norm", None)
+    if gnorm is not None:
+        save("grad_norm", gnorm)
+    flat = trainer.flat
+    numel = flat.data.numel()
+    if numel > DUMP_SAMPLE:
+        g = torch.Generator(device="cpu").manual_seed(20240607)
+        idx = torch.randint(0, numel, (DUMP_SAMPLE,), generator=g)
+        idx = idx.sort().values.to(flat.data.device)
+        save("params_sample", flat.data.reshape(-1)[idx])
+        save("grads_sample", flat.grad.reshape(-1)[idx])
+    else:
+        save("params_sample", flat.data)
+        save("grads_sample", flat.grad)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -42,7 +83,15 @@ def main():
     # in-place CE backward freed the second ~7 GB dlogits buffer, so mb7
     # fits (peak 277.6 GiB) and measures +1.2% over mb6 (20,789 vs 20,542
     # same box); mb8 still OOMs on activations.
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's "
+                         "outputs as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline "
+                         "(none exist yet; a plain run is already minimal)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         os.environ.setdefault("KF_COMM_STATS", "1")  # comm/overlap stats
@@ -133,6 +182,8 @@ def main():
             # how much headroom the overlap has at this N / bucket size)
             out["comm_ms_per_step"] = round(sum(comm_ms) / len(comm_ms), 2)
             out["bucket_mb"] = float(os.environ.get("KF_DDP_BUCKET_MB", "64"))
+        if args.dump_outputs:
+            _dump_outputs(args.dump_outputs, trainer, loss)
         print(json.dumps(out), flush=True)
     if os.environ.get("KF_BENCH_MEM") and device.type == "cuda":
         peak = torch.cuda.max_memory_allocated(device) / (1 << 30)
