@@ -616,18 +616,17 @@ class _FusedQkvAttentionHip(torch.autograd.Function):
         dout = dout.contiguous()
         dqkv = torch.empty_like(qkv)
         delta = torch.empty(B, Hq, S, dtype=torch.float32, device=qkv.device)
+        # the adjoint of the in-place rotation on the dq/dk regions runs in
+        # the backward kernels' store epilogues
         _backend.check(
-            lib.kf_attn_bwd(_p(dqkv), _p_off(dqkv, Hq * D),
-                            _p_off(dqkv, (Hq + Hkv) * D), _p(dout), _p(qkv),
-                            _p_off(qkv, Hq * D), _p_off(qkv, (Hq + Hkv) * D),
-                            _p(o), _fp(lse), _fp(delta), B, S, Hq, Hkv, D,
-                            ts, ts, ts, ts, float(scale), int(causal),
-                            _stream()), "attn_bwd")
-        # adjoint of the in-place rotation on the dq/dk regions
-        _backend.check(
-            lib.kf_rope(_p(dqkv), _p_off(dqkv, Hq * D), _fp(cos), _fp(sin),
-                        _ip_or_null(None), B, S, Hq, Hkv, D, ts, ts, 0, 1,
-                        _stream()), "rope_bwd")
+            lib.kf_attn_bwd_rope(_p(dqkv), _p_off(dqkv, Hq * D),
+                                 _p_off(dqkv, (Hq + Hkv) * D), _p(dout),
+                                 _p(qkv), _p_off(qkv, Hq * D),
+                                 _p_off(qkv, (Hq + Hkv) * D), _p(o),
+                                 _fp(lse), _fp(delta), B, S, Hq, Hkv, D,
+                                 ts, ts, ts, ts, float(scale), int(causal),
+                                 _fp(cos), _fp(sin), 0, _stream()),
+            "attn_bwd_rope")
         return dqkv, None, None, None, None, None, None, None
 
 

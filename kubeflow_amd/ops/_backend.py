@@ -102,6 +102,24 @@ def _configure(lib: ctypes.CDLL) -> None:
         lib.kf_attn_bwd.argtypes = [P, P, P, P, P, P, P, P, FP, FP, I64, I64,
                                     I64, I64, I64, I64, I64, I64, I64, F, I32,
                                     P]
+    if hasattr(lib, "kf_attn_bwd_rope"):
+        # kf_attn_bwd's arguments + cos, sin, pos_offset before the stream
+        lib.kf_attn_bwd_rope.restype = I32
+        lib.kf_attn_bwd_rope.argtypes = [P, P, P, P, P, P, P, P, FP, FP, I64,
+                                         I64, I64, I64, I64, I64, I64, I64,
+                                         I64, F, I32, FP, FP, I64, P]
+    # per-pass entry points of the 8-wave backward (tests / bisection);
+    # the *_rope forms add cos, sin, pos_offset before the stream
+    dq8 = [P, P, P, P, P, FP, FP, I64, I64, I64, I64, I64, I64, I64, F, I32]
+    dkv8 = [P] + dq8
+    for name, args in (("kf_attn_bwd8_dq", dq8), ("kf_attn_bwd8_dkv", dkv8),
+                       ("kf_attn_bwd8_dkv_fused", dkv8)):
+        if hasattr(lib, name):
+            getattr(lib, name).restype = I32
+            getattr(lib, name).argtypes = args + [P]
+        if hasattr(lib, name + "_rope"):
+            getattr(lib, name + "_rope").restype = I32
+            getattr(lib, name + "_rope").argtypes = args + [FP, FP, I64, P]
     lib.kf_layernorm_fwd.restype = I32
     lib.kf_layernorm_fwd.argtypes = [P, FP, FP, P, P, P, I64, I64, F, P]
     lib.kf_layernorm_bwd.restype = I32

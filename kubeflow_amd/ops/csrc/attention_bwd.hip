@@ -361,6 +361,51 @@ extern "C" int kf_attn_bwd8_dkv(void*, void*, const void*, const void*,
                                 int64_t, int64_t, int64_t, int64_t, float,
                                 int, void*);
 
+extern "C" int kf_attn_bwd8_dq_rope(void*, const void*, const void*,
+                                    const void*, const void*, const float*,
+                                    const float*, int64_t, int64_t, int64_t,
+                                    int64_t, int64_t, int64_t, int64_t, float,
+                                    int, const float*, const float*, int64_t,
+                                    void*);
+extern "C" int kf_attn_bwd8_dkv_rope(void*, void*, const void*, const void*,
+                                     const void*, const void*, const float*,
+                                     const float*, int64_t, int64_t, int64_t,
+                                     int64_t, int64_t, int64_t, int64_t,
+                                     float, int, const float*, const float*,
+                                     int64_t, void*);
+extern "C" int kf_attn_bwd8_dkv_fused_rope(void*, void*, const void*,
+                                           const void*, const void*,
+                                           const void*, const float*,
+                                           const float*, int64_t, int64_t,
+                                           int64_t, int64_t, int64_t, int64_t,
+                                           int64_t, float, int, const float*,
+                                           const float*, int64_t, void*);
+
+extern "C" int kf_rope(void*, void*, const float*, const float*,
+                       const int64_t*, int64_t, int64_t, int64_t, int64_t,
+                       int64_t, int64_t, int64_t, int64_t, int, void*);
+
+// dK/dV pass on the 8-wave path: KF_ATTN_BWD_IMPL=1 selects the split
+// dv8 + dk8 pair (bisection), anything else the fused kf_attn_dkv8f kernel.
+static int kf_attn_bwd_impl() {
+  static int cached = -1;
+  if (cached < 0) {
+    const char* e = getenv("KF_ATTN_BWD_IMPL");
+    cached = (e && e[0] == '1') ? 1 : 2;
+  }
+  return cached;
+}
+
+KF_EXPORT int kf_attn_bwd_rope(void* dq, void* dk, void* dv, const void* dout,
+                               const void* q, const void* k, const void* v,
+                               const void* o, const float* lse, float* delta,
+                               int64_t B, int64_t S, int64_t Hq, int64_t Hkv,
+                               int64_t D, int64_t qts, int64_t kts,
+                               int64_t dqts, int64_t dkts, float scale,
+                               int causal, const float* cost,
+                               const float* sint, int64_t pos_offset,
+                               void* stream);
+
 KF_EXPORT int kf_attn_bwd(void* dq, void* dk, void* dv, const void* dout,
                           const void* q, const void* k, const void* v,
                           const void* o, const float* lse, float* delta,
@@ -368,7 +413,28 @@ KF_EXPORT int kf_attn_bwd(void* dq, void* dk, void* dv, const void* dout,
                           int64_t D, int64_t qts, int64_t kts, int64_t dqts,
                           int64_t dkts, float scale, int causal,
                           void* stream) {
+  return kf_attn_bwd_rope(dq, dk, dv, dout, q, k, v, o, lse, delta, B, S, Hq,
+                          Hkv, D, qts, kts, dqts, dkts, scale, causal,
+                          nullptr, nullptr, 0, stream);
+}
+
+// kf_attn_bwd with the RoPE adjoint folded into the dq and dk store
+// epilogues: cost/sint are the fp32 [pos, D/2] tables the forward rotation
+// used and must cover positions pos_offset .. pos_offset + S - 1. With null
+// tables nothing is rotated (plain kf_attn_bwd). Only the 8-wave kernels
+// rotate in their epilogues; the 4-wave path for S % 256 != 0 (small test
+// shapes) launches kf_rope(backward=1) behind its kernels instead.
+KF_EXPORT int kf_attn_bwd_rope(void* dq, void* dk, void* dv, const void* dout,
+                               const void* q, const void* k, const void* v,
+                               const void* o, const float* lse, float* delta,
+                               int64_t B, int64_t S, int64_t Hq, int64_t Hkv,
+                               int64_t D, int64_t qts, int64_t kts,
+                               int64_t dqts, int64_t dkts, float scale,
+                               int causal, const float* cost,
+                               const float* sint, int64_t pos_offset,
+                               void* stream) {
   if (D != AB_D || S % 64 || Hq % Hkv) return (int)hipErrorInvalidValue;
+  if ((cost == nullptr) != (sint == nullptr)) return (int)hipErrorInvalidValue;
   if (qts == 0) qts = Hq * AB_D;
   if (kts == 0) kts = Hkv * AB_D;
   if (dqts == 0) dqts = Hq * AB_D;
@@ -380,11 +446,18 @@ KF_EXPORT int kf_attn_bwd(void* dq, void* dk, void* dv, const void* dout,
   int err = (int)hipGetLastError();
   if (err) return err;
   if (S % 256 == 0) {  // 8-wave swapped path for the training shapes
-    err = kf_attn_bwd8_dq(dq, q, k, v, dout, lse, delta, B, S, Hq, Hkv, qts,
-                          kts, dqts, scale, causal, stream);
+    err = kf_attn_bwd8_dq_rope(dq, q, k, v, dout, lse, delta, B, S, Hq, Hkv,
+                               qts, kts, dqts, scale, causal, cost, sint,
+                               pos_offset, stream);
     if (err) return err;
-    return kf_attn_bwd8_dkv(dk, dv, q, k, v, dout, lse, delta, B, S, Hq, Hkv,
-                            qts, kts, dkts, scale, causal, stream);
+    if (kf_attn_bwd_impl() == 1)
+      return kf_attn_bwd8_dkv_rope(dk, dv, q, k, v, dout, lse, delta, B, S,
+                                   Hq, Hkv, qts, kts, dkts, scale, causal,
+                                   cost, sint, pos_offset, stream);
+    return kf_attn_bwd8_dkv_fused_rope(dk, dv, q, k, v, dout, lse, delta, B,
+                                       S, Hq, Hkv, qts, kts, dkts, scale,
+                                       causal, cost, sint, pos_offset,
+                                       stream);
   }
   dim3 gq((unsigned)(S / 64), (unsigned)Hq, (unsigned)B);
   hipLaunchKernelGGL(kf_attn_dq_kernel, gq, dim3(256), 0, (hipStream_t)stream,
@@ -401,5 +474,8 @@ KF_EXPORT int kf_attn_bwd(void* dq, void* dk, void* dv, const void* dout,
                      (const unsigned short*)k, (const unsigned short*)v,
                      (const unsigned short*)dout, lse, delta, B, (int)S,
                      (int)Hq, (int)Hkv, qts, kts, dkts, scale, causal);
-  return (int)hipGetLastError();
+  err = (int)hipGetLastError();
+  if (err || !cost) return err;
+  return kf_rope(dq, dk, cost, sint, nullptr, B, S, Hq, Hkv, D, dqts, dkts,
+                 pos_offset, 1, stream);
 }

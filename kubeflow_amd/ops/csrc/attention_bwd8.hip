@@ -23,10 +23,26 @@
 //   dQ^T += mfma(tr(K), exch(dS^T))
 //
 // pass dKV (block = b, hkv, 256-row kv-tile; wave = 32 kv rows; loops the
-// GQA group's heads × 64-row q-tiles; split into dV and dK kernels —
-// carrying both accumulators spilled 62 VGPRs in round 1):
+// GQA group's heads × 64-row q-tiles):
 //   S = mfma(Q, K), dP = mfma(dO, V)          Q/dO subtiled in LDS
 //   dV += mfma(exch(P), tr(dO)) ; dK += mfma(exch(dS), tr(Q))
+// Default: ONE fused kernel, kf_attn_dkv8f (32 MFMAs per 32x32 sub-block).
+// Rounds 1-2 split it into dv8 + dk8 (16 + 24 MFMAs, Q/dO streamed and S,
+// exp2 computed twice) because carrying both accumulators spilled 62 VGPRs.
+// That attempt already ran at the 256-register budget — launch_bounds'
+// second argument is waves per SIMD, and dk8 alone takes 252 — so the fused
+// kernel does not get a bigger budget, it needs fewer registers: V
+// fragments parked in LDS, one staging register for lse/delta, 32-bit
+// staging offsets (255 VGPRs, scratch 0; details at the kernel).
+// Measured on MI355X, B7 S4096 Hq32 Hkv8 causal: dv8 + dk8 3.21 ms, dkv8f
+// 2.26 ms per call, bit-identical dK/dV; llama3-8b train step 1368.6 ->
+// 1334.9 ms (profiles/r03_attn_bwd_fused.md). The split pair stays for
+// bisection (KF_ATTN_BWD_IMPL=1).
+//
+// The dq8, dk8 and dkv8f store epilogues optionally apply the RoPE adjoint
+// (cost/sint != nullptr): acc[dt] and acc[dt+2] hold the rotate-half pair
+// (d, d+64) in one lane, so the separate kf_rope(backward=1) pass over
+// dq/dk is not needed.
 
 #include "kf_common.h"
 
@@ -84,6 +100,19 @@ __device__ __forceinline__ unsigned kf_tr_lane_off(int lane) {
   const int g = lane >> 4;
   return (unsigned)(((g & 1) << 11) + ((g >> 1) << 8) + ((lane & 15) << 3));
 }
+
+// RoPE adjoint on one rotate-half pair (d, d+64) held as fp32 accumulators.
+// Rounds to bf16 FIRST, then applies the inverse rotation with the same
+// mul + fma forms kf_rope_kernel(backward=1) compiles to, so "rotate in the
+// store epilogue" is bit-identical to "store bf16, then kf_rope".
+#define KF_ROPE_ADJ_PAIR(x1, x2, c, s)                                \
+  {                                                                   \
+    const float a_ = kf_bf16_to_f32(kf_f32_to_bf16(x1));              \
+    const float b_ = kf_bf16_to_f32(kf_f32_to_bf16(x2));              \
+    const float t1_ = b_ * (s), t2_ = a_ * (s);                       \
+    (x1) = __builtin_fmaf(a_, (c), t1_);                              \
+    (x2) = __builtin_fmaf(b_, (c), -t2_);                             \
+  }
 
 // accumulate acc[dt] += mfma(tr-frag(dt), pb[step]) over dt=0..3 with a
 // 1-deep tr_read prefetch (identical loop to the fwd v4 pv_block).
@@ -161,7 +190,9 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dq8_kernel(
     const unsigned short* __restrict__ k, const unsigned short* __restrict__ v,
     const unsigned short* __restrict__ dout, const float* __restrict__ lse,
     const float* __restrict__ delta, int64_t B, int S, int Hq, int Hkv,
-    int64_t qts, int64_t kts, int64_t dqts, float scale, int causal) {
+    int64_t qts, int64_t kts, int64_t dqts, float scale, int causal,
+    const float* __restrict__ cost, const float* __restrict__ sint,
+    int64_t pos_offset) {
   __shared__ unsigned char k_lds[2][DQ8_KT * AB_D * 2];  // subtiled
   __shared__ unsigned char v_lds[2][DQ8_KT * AB_D * 2];  // subtiled
 
@@ -290,6 +321,25 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dq8_kernel(
     __syncthreads();
   }
 
+  // optional RoPE adjoint (cost != nullptr): acc[dt] / acc[dt+2] hold the
+  // rotate-half pair (d, d+64) of this lane's q row
+  if (cost) {
+    const int64_t cb = (pos_offset + qrow_g) * (AB_D / 2) + 4 * hi;
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq) {
+        const kf_float4 c4 =
+            *reinterpret_cast<const kf_float4*>(cost + cb + dt * 32 + 8 * rq);
+        const kf_float4 s4 =
+            *reinterpret_cast<const kf_float4*>(sint + cb + dt * 32 + 8 * rq);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          KF_ROPE_ADJ_PAIR(dqacc[dt][rq * 4 + j], dqacc[dt + 2][rq * 4 + j],
+                           c4[j], s4[j]);
+      }
+  }
+
   // epilogue: dQ^T regs -> dq (4 consecutive d per quad -> b64 stores)
   const int64_t dqb = (b * S + qrow_g) * dqts + (int64_t)hq * AB_D;
 #pragma unroll
@@ -307,9 +357,10 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dq8_kernel(
 }
 
 // --------------------------------------------------------------- pass dKV --
-// Split into dV and dK kernels: carrying both 64-register accumulators in
-// one kernel spilled 62 VGPRs at the 2-waves/SIMD budget; recomputing S in
-// a second kernel (+25% MFMA) is far cheaper than scratch traffic.
+// Split dV and dK kernels (KF_ATTN_BWD_IMPL=1; the default is the fused
+// kf_attn_dkv8f below): carrying both 64-register accumulators in one
+// kernel spilled 62 VGPRs at the 2-waves/SIMD budget, and recomputing S in
+// a second kernel (+25% MFMA) was far cheaper than scratch traffic.
 #define DKV8_KT 256   // kv rows per block (8 waves x 32)
 #define DKV8_QT 64    // q rows per LDS tile
 
@@ -460,7 +511,9 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dk8_kernel(
     const unsigned short* __restrict__ k, const unsigned short* __restrict__ v,
     const unsigned short* __restrict__ dout, const float* __restrict__ lse,
     const float* __restrict__ delta, int64_t B, int S, int Hq, int Hkv,
-    int64_t qts, int64_t kts, int64_t dkts, float scale, int causal) {
+    int64_t qts, int64_t kts, int64_t dkts, float scale, int causal,
+    const float* __restrict__ cost, const float* __restrict__ sint,
+    int64_t pos_offset) {
   __shared__ unsigned char q_lds[2][DKV8_QT * AB_D * 2];   // subtiled
   __shared__ unsigned char do_lds[2][DKV8_QT * AB_D * 2];  // subtiled
   __shared__ float lse_s2[2][DKV8_QT], dlt_s2[2][DKV8_QT];
@@ -598,10 +651,256 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dk8_kernel(
   for (int r = 0; r < 16; ++r) {
     const int kvr = kvbase + (r & 3) + 8 * (r >> 2);
     const int64_t base = (b * S + kvr) * dkts + (int64_t)hkv * AB_D;
+    if (cost) {  // RoPE adjoint: (acc[dt], acc[dt+2]) is the pair (d, d+64)
+      const int64_t cb = (pos_offset + kvr) * (AB_D / 2) + l31;
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt)
+        KF_ROPE_ADJ_PAIR(dkacc[dt][r], dkacc[dt + 2][r], cost[cb + dt * 32],
+                         sint[cb + dt * 32]);
+    }
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
       dk[base + dt * 32 + l31] = kf_f32_to_bf16(dkacc[dt][r]);
   }
+}
+
+// --------------------------------------------------------- fused pass dKV --
+// One pass producing dK and dV: S and P are computed once per sub-block and
+// Q/dO are streamed once, so a 32x32 sub-block costs 32 MFMAs (8 S + 8 dP +
+// 8 P^T dO + 8 dS^T Q) where the dv8 + dk8 pair spends 40.
+//
+// Shape: the split kernels' — 512 threads, 8 waves x 32 kv rows, one block
+// per CU, 2 waves/SIMD and therefore 256 registers per lane
+// (__launch_bounds__'s second argument counts waves per SIMD: dk8 already
+// uses 252 of them, it never ran at a 128-register budget). dkacc 64 +
+// dvacc 64 + K and V fragments 64 + sacc/dpacc 32 + staging 16 + tr
+// temporaries 16 is ~260 before addresses and spilled, so:
+//  * the V B-fragments are parked in LDS (64 KiB, each lane re-reads only
+//    the 8 chunks it wrote itself, one extra ds_read_b128 per dP MFMA);
+//  * lse and delta share one staging register (a two-variable version went
+//    through a stack slot);
+//  * the per-lane staging offsets are 32-bit on a wave-uniform base.
+// With a 4-wave, 128-kv-row block the compiler took 373 registers, i.e. one
+// 4-wave block per CU: rejected before any run.
+// Per kv row the work and the summation order are exactly those of dv8/dk8
+// (same MFMA shape, q sub-blocks ascending within head order, d contracted
+// in the same 8 steps), so dK and dV are bit-identical to the split kernels.
+//
+// Resource usage (hipcc -Rpass-analysis=kernel-resource-usage, gfx950):
+//   255 VGPRs, 0 AGPRs, scratch 0, 2 waves/SIMD, LDS 132,096 B/block.
+#define DKVF_WAVES 8
+#define DKVF_THREADS (DKVF_WAVES * KF_WAVE)
+#define DKVF_KT (DKVF_WAVES * 32)  // kv rows per block
+#define DKVF_NST (DKV8_QT * 16 / DKVF_THREADS)  // staged b128 per thread
+#define DKVF_SLAB (DKV8_QT * 16 * 2)  // bytes per 16-wide d-slab of a tile
+
+__global__ __launch_bounds__(DKVF_THREADS, 2) void kf_attn_dkv8f_kernel(
+    unsigned short* __restrict__ dk, unsigned short* __restrict__ dv,
+    const unsigned short* __restrict__ q, const unsigned short* __restrict__ k,
+    const unsigned short* __restrict__ v,
+    const unsigned short* __restrict__ dout, const float* __restrict__ lse,
+    const float* __restrict__ delta, int64_t B, int S, int Hq, int Hkv,
+    int64_t qts, int64_t kts, int64_t dkts, float scale, int causal,
+    const float* __restrict__ cost, const float* __restrict__ sint,
+    int64_t pos_offset) {
+  __shared__ unsigned char q_lds[2][DKV8_QT * AB_D * 2];   // subtiled
+  __shared__ unsigned char do_lds[2][DKV8_QT * AB_D * 2];  // subtiled
+  __shared__ float lse_s3[2][DKV8_QT], dlt_s3[2][DKV8_QT];
+  // V B-fragments parked in LDS: every lane writes its own 8 chunks once and
+  // reads back only those (no barrier needed), subtiled like q_lds so the
+  // b128 reads bank exactly like the Q/dO row-chunk reads
+  __shared__ unsigned char v_lds[DKVF_WAVES / 2][DKV8_QT * AB_D * 2];
+
+  const int kt = blockIdx.x / (Hkv * (int)B);  // LPT decode (see dv8)
+  const int rest = blockIdx.x % (Hkv * (int)B);
+  const int hkv = rest % Hkv;
+  const int64_t b = rest / Hkv;
+  const int g = Hq / Hkv;
+  const int tid = threadIdx.x;
+  const int w = tid / KF_WAVE;
+  const int lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
+  const int kvrow_g = kt * DKVF_KT + w * 32 + l31;
+  const int wave_kv_min = kt * DKVF_KT + w * 32;
+  const float scale2 = scale * AB_LOG2E;
+
+  const unsigned short* kvb_k =
+      k + (b * S + kvrow_g) * kts + (int64_t)hkv * AB_D;
+  const unsigned short* kvb_v =
+      v + (b * S + kvrow_g) * kts + (int64_t)hkv * AB_D;
+  kf_bf16x8 kbf[8];  // persistent K B-fragments (see dv8 note)
+  // chunk kk of the lane's row lives in d-slab kk: kf_subrow8(r, kk * 32 +
+  // hi * 16) == kf_subrow8(r, hi * 16) + kk * DKVF_SLAB (64 rows x 16 d x 2 B)
+  unsigned char* vfrag =
+      v_lds[w >> 1] + kf_subrow8((w & 1) * 32 + l31, hi * 16);
+#pragma unroll
+  for (int kk = 0; kk < 8; ++kk) {
+    kbf[kk] =
+        *reinterpret_cast<const kf_bf16x8*>(kvb_k + kk * 16 + hi * 8);
+    *reinterpret_cast<kf_bf16x8*>(vfrag + kk * DKVF_SLAB) =
+        *reinterpret_cast<const kf_bf16x8*>(kvb_v + kk * 16 + hi * 8);
+  }
+
+  kf_f32x16 dkacc[4], dvacc[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    dkacc[i] = kf_f32x16{0.f};
+    dvacc[i] = kf_f32x16{0.f};
+  }
+
+  const int qt0 = causal ? (kt * DKVF_KT) / DKV8_QT : 0;
+  const int nqt = S / DKV8_QT;
+  const int per_head = nqt - qt0;
+  const int total = g * per_head;
+  const int c8 = tid & 15;
+  const unsigned tr_off = kf_tr_lane_off(lane);
+  // per-lane staging offsets kept 32-bit (uniform 64-bit base + lane offset)
+  constexpr int kRowsPerPass = DKVF_THREADS / 16;
+  const unsigned qoff = (unsigned)((tid >> 4) * (int)qts + c8 * 8);
+  const unsigned dooff = (unsigned)((tid >> 4) * Hq * AB_D + c8 * 8);
+
+  kf_short8 sq[DKVF_NST], sd[DKVF_NST];
+  float rc_ld = 0.f;  // row constant: lse (tid < 64) or delta (tid < 128)
+  auto stage_load = [&](int flat) {
+    const int hq = hkv * g + flat / per_head;
+    const int qt = qt0 + flat % per_head;
+    const unsigned short* qg =
+        q + (b * S + qt * DKV8_QT) * qts + (int64_t)hq * AB_D;
+    const unsigned short* dog =
+        dout + ((b * S + qt * DKV8_QT) * (int64_t)Hq + hq) * AB_D;
+    if (tid < 2 * DKV8_QT) {
+      const float* rc = tid < DKV8_QT ? lse : delta;
+      rc_ld = rc[(b * Hq + hq) * (int64_t)S + qt * DKV8_QT +
+                 (tid & (DKV8_QT - 1))];
+    }
+#pragma unroll
+    for (int j = 0; j < DKVF_NST; ++j) {
+      sq[j] = *reinterpret_cast<const kf_short8*>(
+          qg + j * kRowsPerPass * qts + qoff);
+      sd[j] = *reinterpret_cast<const kf_short8*>(
+          dog + j * kRowsPerPass * (int64_t)Hq * AB_D + dooff);
+    }
+  };
+  auto stage_write = [&](int buf) {
+    if (tid < DKV8_QT) lse_s3[buf][tid] = rc_ld * AB_LOG2E;
+    else if (tid < 2 * DKV8_QT) dlt_s3[buf][tid - DKV8_QT] = rc_ld;
+#pragma unroll
+    for (int j = 0; j < DKVF_NST; ++j) {
+      const int sr = (tid + j * DKVF_THREADS) >> 4;
+      *reinterpret_cast<kf_short8*>(q_lds[buf] + 2 * kf_vsub8(sr, c8 * 8)) =
+          sq[j];
+      *reinterpret_cast<kf_short8*>(do_lds[buf] + 2 * kf_vsub8(sr, c8 * 8)) =
+          sd[j];
+    }
+  };
+
+  stage_load(0);
+  stage_write(0);
+  __syncthreads();
+  for (int flat = 0; flat < total; ++flat) {
+    const int cur = flat & 1;
+    const bool have_next = flat + 1 < total;
+    if (have_next) stage_load(flat + 1);
+    const int qt = qt0 + flat % per_head;
+
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) {
+      const int q_lo = qt * DKV8_QT + mt * 32;
+      if (causal && q_lo + 31 < wave_kv_min) continue;
+      kf_f32x16 sacc = kf_f32x16{0.f}, dpacc = kf_f32x16{0.f};
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int kk = 0; kk < 8; ++kk) {
+        kf_bf16x8 qa = *reinterpret_cast<const kf_bf16x8*>(
+            q_lds[cur] + kf_subrow8(mt * 32 + l31, kk * 32 + hi * 16));
+        sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, kbf[kk], sacc, 0,
+                                                       0, 0);
+        kf_bf16x8 da = *reinterpret_cast<const kf_bf16x8*>(
+            do_lds[cur] + kf_subrow8(mt * 32 + l31, kk * 32 + hi * 16));
+        kf_bf16x8 vb =
+            *reinterpret_cast<const kf_bf16x8*>(vfrag + kk * DKVF_SLAB);
+        dpacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, vb, dpacc, 0, 0,
+                                                        0);
+      }
+      __builtin_amdgcn_s_setprio(0);
+
+      // P once (exactly dv8's expression), then dS from it (dk8's)
+      const int q0 = mt * 32 + hi * 4;
+      const bool need_mask = causal && q_lo <= kt * DKVF_KT + w * 32 + 31;
+      if (need_mask) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int ql = q0 + (r & 3) + 8 * (r >> 2);
+          const int qq = qt * DKV8_QT + ql;
+          sacc[r] = (kvrow_g > qq)
+                        ? 0.f
+                        : kf_exp2b(sacc[r] * scale2 - lse_s3[cur][ql]);
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int ql = q0 + (r & 3) + 8 * (r >> 2);
+          sacc[r] = kf_exp2b(sacc[r] * scale2 - lse_s3[cur][ql]);
+        }
+      }
+      kf_bf16x8 pa0 = kf_exchange8(sacc, 0), pa1 = kf_exchange8(sacc, 8);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int ql = q0 + (r & 3) + 8 * (r >> 2);
+        sacc[r] = sacc[r] * (dpacc[r] - dlt_s3[cur][ql]) * scale;  // dS
+      }
+      kf_bf16x8 ds0 = kf_exchange8(sacc, 0), ds1 = kf_exchange8(sacc, 8);
+
+      const unsigned vbase_do =
+          (unsigned)(size_t)(do_lds[cur]) + tr_off + (mt << 10);
+      KF_TR_ACC_LOOP_B(dvacc, vbase_do, pa0, pa1);
+      const unsigned vbase_q =
+          (unsigned)(size_t)(q_lds[cur]) + tr_off + (mt << 10);
+      KF_TR_ACC_LOOP_B(dkacc, vbase_q, ds0, ds1);
+    }
+    if (have_next) stage_write(cur ^ 1);
+    __syncthreads();
+  }
+
+  const int kvbase = kt * DKVF_KT + w * 32 + hi * 4;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int kvr = kvbase + (r & 3) + 8 * (r >> 2);
+    const int64_t base = (b * S + kvr) * dkts + (int64_t)hkv * AB_D;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+      dv[base + dt * 32 + l31] = kf_f32_to_bf16(dvacc[dt][r]);
+    if (cost) {  // RoPE adjoint on dK only (see dk8)
+      const int64_t cb = (pos_offset + kvr) * (AB_D / 2) + l31;
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt)
+        KF_ROPE_ADJ_PAIR(dkacc[dt][r], dkacc[dt + 2][r], cost[cb + dt * 32],
+                         sint[cb + dt * 32]);
+    }
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+      dk[base + dt * 32 + l31] = kf_f32_to_bf16(dkacc[dt][r]);
+  }
+}
+
+// ----------------------------------------------------------- entry points --
+// The *_rope variants take cos/sin tables [pos, D/2] fp32 and a position
+// offset; nullptr tables mean no rotation. dk and dv must not alias.
+KF_EXPORT int kf_attn_bwd8_dq_rope(void* dq, const void* q, const void* k,
+                                   const void* v, const void* dout,
+                                   const float* lse, const float* delta,
+                                   int64_t B, int64_t S, int64_t Hq,
+                                   int64_t Hkv, int64_t qts, int64_t kts,
+                                   int64_t dqts, float scale, int causal,
+                                   const float* cost, const float* sint,
+                                   int64_t pos_offset, void* stream) {
+  dim3 gq((unsigned)((S / DQ8_QT) * Hq * B), 1, 1);
+  hipLaunchKernelGGL(kf_attn_dq8_kernel, gq, dim3(512), 0,
+                     (hipStream_t)stream, (unsigned short*)dq,
+                     (const unsigned short*)q, (const unsigned short*)k,
+                     (const unsigned short*)v, (const unsigned short*)dout,
+                     lse, delta, B, (int)S, (int)Hq, (int)Hkv, qts, kts, dqts,
+                     scale, causal, cost, sint, pos_offset);
+  return (int)hipGetLastError();
 }
 
 KF_EXPORT int kf_attn_bwd8_dq(void* dq, const void* q, const void* k,
@@ -610,22 +909,21 @@ KF_EXPORT int kf_attn_bwd8_dq(void* dq, const void* q, const void* k,
                               int64_t S, int64_t Hq, int64_t Hkv, int64_t qts,
                               int64_t kts, int64_t dqts, float scale,
                               int causal, void* stream) {
-  dim3 gq((unsigned)((S / DQ8_QT) * Hq * B), 1, 1);
-  hipLaunchKernelGGL(kf_attn_dq8_kernel, gq, dim3(512), 0,
-                     (hipStream_t)stream, (unsigned short*)dq,
-                     (const unsigned short*)q, (const unsigned short*)k,
-                     (const unsigned short*)v, (const unsigned short*)dout,
-                     lse, delta, B, (int)S, (int)Hq, (int)Hkv, qts, kts, dqts,
-                     scale, causal);
-  return (int)hipGetLastError();
+  return kf_attn_bwd8_dq_rope(dq, q, k, v, dout, lse, delta, B, S, Hq, Hkv,
+                              qts, kts, dqts, scale, causal, nullptr, nullptr,
+                              0, stream);
 }
 
-KF_EXPORT int kf_attn_bwd8_dkv(void* dk, void* dv, const void* q,
-                               const void* k, const void* v, const void* dout,
-                               const float* lse, const float* delta,
-                               int64_t B, int64_t S, int64_t Hq, int64_t Hkv,
-                               int64_t qts, int64_t kts, int64_t dkts,
-                               float scale, int causal, void* stream) {
+// split pair: dv8 then dk8
+KF_EXPORT int kf_attn_bwd8_dkv_rope(void* dk, void* dv, const void* q,
+                                    const void* k, const void* v,
+                                    const void* dout, const float* lse,
+                                    const float* delta, int64_t B, int64_t S,
+                                    int64_t Hq, int64_t Hkv, int64_t qts,
+                                    int64_t kts, int64_t dkts, float scale,
+                                    int causal, const float* cost,
+                                    const float* sint, int64_t pos_offset,
+                                    void* stream) {
   dim3 gkv((unsigned)((S / DKV8_KT) * Hkv * B), 1, 1);
   hipLaunchKernelGGL(kf_attn_dv8_kernel, gkv, dim3(512), 0,
                      (hipStream_t)stream, (unsigned short*)dv,
@@ -639,6 +937,48 @@ KF_EXPORT int kf_attn_bwd8_dkv(void* dk, void* dv, const void* q,
                      (const unsigned short*)q, (const unsigned short*)k,
                      (const unsigned short*)v, (const unsigned short*)dout,
                      lse, delta, B, (int)S, (int)Hq, (int)Hkv, qts, kts,
-                     dkts, scale, causal);
+                     dkts, scale, causal, cost, sint, pos_offset);
   return (int)hipGetLastError();
+}
+
+KF_EXPORT int kf_attn_bwd8_dkv(void* dk, void* dv, const void* q,
+                               const void* k, const void* v, const void* dout,
+                               const float* lse, const float* delta,
+                               int64_t B, int64_t S, int64_t Hq, int64_t Hkv,
+                               int64_t qts, int64_t kts, int64_t dkts,
+                               float scale, int causal, void* stream) {
+  return kf_attn_bwd8_dkv_rope(dk, dv, q, k, v, dout, lse, delta, B, S, Hq,
+                               Hkv, qts, kts, dkts, scale, causal, nullptr,
+                               nullptr, 0, stream);
+}
+
+// fused dK+dV pass (S % 128 == 0)
+KF_EXPORT int kf_attn_bwd8_dkv_fused_rope(
+    void* dk, void* dv, const void* q, const void* k, const void* v,
+    const void* dout, const float* lse, const float* delta, int64_t B,
+    int64_t S, int64_t Hq, int64_t Hkv, int64_t qts, int64_t kts,
+    int64_t dkts, float scale, int causal, const float* cost,
+    const float* sint, int64_t pos_offset, void* stream) {
+  if (S % DKVF_KT || Hq % Hkv) return (int)hipErrorInvalidValue;
+  dim3 gkv((unsigned)((S / DKVF_KT) * Hkv * B), 1, 1);
+  hipLaunchKernelGGL(kf_attn_dkv8f_kernel, gkv, dim3(DKVF_THREADS), 0,
+                     (hipStream_t)stream, (unsigned short*)dk,
+                     (unsigned short*)dv, (const unsigned short*)q,
+                     (const unsigned short*)k, (const unsigned short*)v,
+                     (const unsigned short*)dout, lse, delta, B, (int)S,
+                     (int)Hq, (int)Hkv, qts, kts, dkts, scale, causal, cost,
+                     sint, pos_offset);
+  return (int)hipGetLastError();
+}
+
+KF_EXPORT int kf_attn_bwd8_dkv_fused(void* dk, void* dv, const void* q,
+                                     const void* k, const void* v,
+                                     const void* dout, const float* lse,
+                                     const float* delta, int64_t B, int64_t S,
+                                     int64_t Hq, int64_t Hkv, int64_t qts,
+                                     int64_t kts, int64_t dkts, float scale,
+                                     int causal, void* stream) {
+  return kf_attn_bwd8_dkv_fused_rope(dk, dv, q, k, v, dout, lse, delta, B, S,
+                                     Hq, Hkv, qts, kts, dkts, scale, causal,
+                                     nullptr, nullptr, 0, stream);
 }
