@@ -391,6 +391,122 @@ class _FlashAttnHip(torch.autograd.Function):
         return dq, dk, dv, None, None
 
 
+_ATTN_DIMS = (64, 128)  # head dims with a native attention family
+
+
+def _attn64_enabled() -> bool:
+    """KF_ATTN_D64=0: bisection switch — D == 64 attention on the GPU runs
+    the torch reference math instead of attention_d64.hip."""
+    return os.environ.get("KF_ATTN_D64", "1") != "0"
+
+
+def _check_head_dim(D: int) -> None:
+    if D not in _ATTN_DIMS:
+        raise ValueError(
+            f"native attention supports head_dim in {_ATTN_DIMS}, got {D}")
+
+
+def _row_stride(t: torch.Tensor) -> Optional[int]:
+    """Token-row stride (elements) if the kernels can read t [B,S,H,D] in
+    place — heads packed, uniform row stride across the batch, 16-byte
+    aligned (the split views of a fused QKV projection) — else None."""
+    B, S, H, D = t.shape
+    rs = t.stride(1)
+    if (t.stride(3) == 1 and t.stride(2) == D and rs >= H * D and rs % 8 == 0
+            and (B == 1 or t.stride(0) == S * rs)
+            and t.data_ptr() % 16 == 0):
+        return rs
+    return None
+
+
+def _attn64_fwd(q, k, v, causal, scale, kv_len):
+    """kf_attn64_fwd on [B,S,H,64] bf16 tensors, S % 128 == 0. Returns
+    (o, lse, q, k, v, qts, kts) with q/k/v as actually passed."""
+    lib = _backend.require()
+    B, S, Hq, D = q.shape
+    Hkv = k.shape[2]
+    qts = _row_stride(q)
+    if qts is None:
+        q = q.contiguous()
+        qts = Hq * D
+    kts = _row_stride(k)
+    if kts is None or _row_stride(v) != kts:
+        k, v = k.contiguous(), v.contiguous()
+        kts = Hkv * D
+    o = torch.empty(B, S, Hq, D, dtype=q.dtype, device=q.device)
+    lse = torch.empty(B, Hq, S, dtype=torch.float32, device=q.device)
+    _backend.check(
+        lib.kf_attn64_fwd(_p(o), _fp(lse), _p(q), _p(k), _p(v), B, S, Hq,
+                          Hkv, qts, kts, float(scale), int(causal),
+                          int(kv_len), _stream()), "attn64_fwd")
+    return o, lse, q, k, v, qts, kts
+
+
+class _FlashAttn64Hip(torch.autograd.Function):
+    """Head-dim-64 family (attention_d64.hip): forward + deterministic
+    two-pass backward, kv rows >= kv_len never attended."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, causal, scale, kv_len):
+        o, lse, q, k, v, qts, kts = _attn64_fwd(q, k, v, causal, scale,
+                                                kv_len)
+        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.meta = (causal, scale, kv_len, qts, kts)
+        return o
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _backend.require()
+        q, k, v, o, lse = ctx.saved_tensors
+        causal, scale, kv_len, qts, kts = ctx.meta
+        B, S, Hq, D = q.shape
+        Hkv = k.shape[2]
+        dout = dout.contiguous()
+        dq = torch.empty(B, S, Hq, D, dtype=q.dtype, device=q.device)
+        dk = torch.empty(B, S, Hkv, D, dtype=k.dtype, device=k.device)
+        dv = torch.empty_like(dk)
+        delta = torch.empty(B, Hq, S, dtype=torch.float32, device=q.device)
+        _backend.check(
+            lib.kf_attn64_bwd(_p(dq), _p(dk), _p(dv), _p(dout), _p(q), _p(k),
+                              _p(v), _p(o), _fp(lse), _fp(delta), B, S, Hq,
+                              Hkv, qts, kts, float(scale), int(causal),
+                              int(kv_len), _stream()), "attn64_bwd")
+        return dq, dk, dv, None, None, None
+
+
+def _pad_rows(t: torch.Tensor, pad: int) -> torch.Tensor:
+    return torch.cat(
+        [t, t.new_zeros(t.shape[0], pad, t.shape[2], t.shape[3])], dim=1)
+
+
+def _flash_attention64(q, k, v, causal, scale, kv_len):
+    """D == 64 native route: any S (zero-padded to a 128 multiple; for
+    non-causal input the pad rows are masked through kv_len, padded q rows
+    are sliced off and so receive zero dout)."""
+    if q.dtype != torch.bfloat16:
+        raise ValueError(f"native attention needs bf16 inputs, got {q.dtype}")
+    S = q.shape[1]
+    if kv_len is None:
+        kv_len = S
+    pad = (128 - S % 128) % 128
+    if pad:
+        q, k, v = _pad_rows(q, pad), _pad_rows(k, pad), _pad_rows(v, pad)
+        if causal:
+            kv_len = S + pad  # pad keys are causally masked for real queries
+    o = _FlashAttn64Hip.apply(q, k, v, causal, scale, kv_len)
+    return o[:, :S] if pad else o
+
+
+def _sdpa_ref(q, k, v, causal, scale, kv_len):
+    """Reference math in bshd (differentiable): k/v sliced to kv_len, so
+    autograd yields zero gradient rows past it."""
+    if kv_len is not None:
+        k, v = k[:, :kv_len], v[:, :kv_len]
+    o = reference.sdpa(q.transpose(1, 2), k.transpose(1, 2),
+                       v.transpose(1, 2), causal=causal, scale=scale)
+    return o.transpose(1, 2)
+
+
 def flash_attention_rect(q: torch.Tensor, k: torch.Tensor,
                          v: torch.Tensor, q_offset: int,
                          scale: Optional[float] = None) -> torch.Tensor:
@@ -464,10 +580,16 @@ def masked_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     beyond kv_len are padding and must not be attended. Uses the
     rectangular-causal kernel with q_offset = kv_len, which makes every
     query's limit min(row + kv_len, kv_len-1) = kv_len-1 (inference
-    only, no autograd; D == 128 on the native path)."""
+    only, no autograd) at D == 128; at D == 64 the mask is built into
+    kf_attn64_fwd (no K/V repack copies)."""
     B, S, Hq, D = q.shape
     if scale is None:
         scale = D ** -0.5
+    if _use_native(q):
+        _check_head_dim(D)
+    if _use_native(q) and D == 64 and _attn64_enabled():
+        with torch.no_grad():
+            return _flash_attention64(q, k, v, False, scale, kv_len)
     if _use_native(q) and D == 128:
         lib = _backend.require()
         Hkv = k.shape[2]
@@ -500,18 +622,42 @@ def masked_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
 
 
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
-                    causal: bool = True, scale: Optional[float] = None):
+                    causal: bool = True, scale: Optional[float] = None,
+                    kv_len: Optional[int] = None):
     """bshd layout: q [B,S,Hq,D], k/v [B,S,Hkv,D] -> o [B,S,Hq,D].
 
-    The CDNA4 kernel tiles q in 128-row blocks; for causal attention,
-    sequences are zero-padded to a 128 multiple here (padded key rows are
-    causally masked for every real query, so results are exact) and the
-    output is sliced back. Non-causal input must already satisfy
-    seq_len % 128 == 0.
+    kv_len (non-causal only): key/value rows >= kv_len are padding and are
+    never attended; their gradients are zero. Works under autograd.
+
+    The CDNA4 kernels tile q in 128-row blocks. D == 128: causal sequences
+    are zero-padded to a 128 multiple here (padded key rows are causally
+    masked for every real query, so results are exact) and the output is
+    sliced back; non-causal input must already satisfy seq_len % 128 == 0
+    and kv_len is not supported (see masked_attention). D == 64
+    (attention_d64.hip): any seq_len, causal or not — non-causal input is
+    zero-padded too and the pad rows are masked through kv_len.
+    KF_ATTN_D64=0 sends D == 64 to the torch reference math (bisection).
     """
+    D = q.shape[-1]
     if scale is None:
-        scale = q.shape[-1] ** -0.5
+        scale = D ** -0.5
+    if kv_len is not None:
+        if causal:
+            raise ValueError("flash_attention: kv_len is non-causal only")
+        kv_len = int(kv_len)
+        if not 1 <= kv_len <= k.shape[1]:
+            raise ValueError(
+                f"kv_len must be in [1, {k.shape[1]}], got {kv_len}")
     if _use_native(q):
+        _check_head_dim(D)
+        if D == 64:
+            if _attn64_enabled():
+                return _flash_attention64(q, k, v, causal, scale, kv_len)
+            return _sdpa_ref(q, k, v, causal, scale, kv_len)
+        if kv_len is not None:
+            raise ValueError(
+                "flash_attention: kv_len needs head_dim 64 on the native "
+                "path; for head_dim 128 use masked_attention (inference)")
         S = q.shape[1]
         pad = (128 - S % 128) % 128
         if pad:
@@ -526,10 +672,7 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
             v = torch.cat([v, zk], dim=1)
             return _FlashAttnHip.apply(q, k, v, causal, scale)[:, :S]
         return _FlashAttnHip.apply(q, k, v, causal, scale)
-    # reference path works in bhsd
-    qt, kt, vt = (t.transpose(1, 2) for t in (q, k, v))
-    o = reference.sdpa(qt, kt, vt, causal=causal, scale=scale)
-    return o.transpose(1, 2)
+    return _sdpa_ref(q, k, v, causal, scale, kv_len)
 
 
 def _p_off(t: torch.Tensor, elem_off: int) -> ctypes.c_void_p:

@@ -120,6 +120,16 @@ def _configure(lib: ctypes.CDLL) -> None:
         if hasattr(lib, name + "_rope"):
             getattr(lib, name + "_rope").restype = I32
             getattr(lib, name + "_rope").argtypes = args + [FP, FP, I64, P]
+    # head-dim-64 family (attention_d64.hip): ..., qts, kts, scale, causal,
+    # kv_len, stream
+    if hasattr(lib, "kf_attn64_fwd"):
+        lib.kf_attn64_fwd.restype = I32
+        lib.kf_attn64_fwd.argtypes = [P, FP, P, P, P, I64, I64, I64, I64,
+                                      I64, I64, F, I32, I64, P]
+    if hasattr(lib, "kf_attn64_bwd"):
+        lib.kf_attn64_bwd.restype = I32
+        lib.kf_attn64_bwd.argtypes = [P, P, P, P, P, P, P, P, FP, FP, I64,
+                                      I64, I64, I64, I64, I64, F, I32, I64, P]
     lib.kf_layernorm_fwd.restype = I32
     lib.kf_layernorm_fwd.argtypes = [P, FP, FP, P, P, P, I64, I64, F, P]
     lib.kf_layernorm_bwd.restype = I32

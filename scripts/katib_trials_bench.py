@@ -1,6 +1,11 @@
 """Measured Katib trial throughput (VERDICT round-1 item 8): N concurrent
 BERT fine-tune trials sharing the available GPUs via gpu_shared
-co-scheduling. Prints one JSON line with measured trials/hour."""
+co-scheduling. Prints one JSON line with measured trials/hour.
+
+usage: katib_trials_bench.py [parallel] [total] [steps] [--model NAME]
+(--model defaults to bert-base-hd128, the config behind the published
+number; bert-base is the real 12 x 64 config)."""
+import argparse
 import json
 import os
 import sys
@@ -19,9 +24,13 @@ PARAMS = [
 
 
 def main():
-    parallel = int(sys.argv[1]) if len(sys.argv) > 1 else 2
-    total = int(sys.argv[2]) if len(sys.argv) > 2 else 6
-    steps = int(sys.argv[3]) if len(sys.argv) > 3 else 50
+    ap = argparse.ArgumentParser()
+    ap.add_argument("parallel", nargs="?", type=int, default=2)
+    ap.add_argument("total", nargs="?", type=int, default=6)
+    ap.add_argument("steps", nargs="?", type=int, default=50)
+    ap.add_argument("--model", default="bert-base-hd128")
+    args = ap.parse_args()
+    parallel, total, steps = args.parallel, args.total, args.steps
     root = os.path.join("/tmp", f"katib-bench-{int(time.time())}")
     with Platform(root_dir=root) as plat:
         exp = new_object("Experiment", "bert-hpo", "default", spec={
@@ -32,7 +41,7 @@ def main():
             "maxTrialCount": total,
             "maxFailedTrialCount": 2,
             "parameters": PARAMS,
-            "trialTemplate": {"model": "bert-base-hd128", "steps": steps,
+            "trialTemplate": {"model": args.model, "steps": steps,
                               "micro_batch": 32, "seq_len": 512,
                               "gpus_per_replica": 1, "gpu_shared": True,
                               "gpu_memory": "48Gi", "status_every": 10,
@@ -56,7 +65,7 @@ def main():
             "parallel": parallel,
             "wall_s": round(wall, 1),
             "steps_per_trial": steps,
-            "model": "bert-base-hd128",
+            "model": args.model,
             "gpus": plat.scheduler.inv.n_gpus,
             "measured": True,
         }), flush=True)
