@@ -12,6 +12,12 @@
 // Rows with target == ignore_index contribute 0 loss and 0 grad; the valid
 // count is handled by the caller (scale). loss_sum accumulation is one
 // atomicAdd per row (guide G12: block-reduce first, one atomic per block).
+//
+// Alignment: row t starts at logits + t*V, which is 16-byte aligned for every
+// t only when V % CE_VEC == 0. Any other V takes the scalar loop for the
+// WHOLE row (nvec = 0) in both kernels — a vector prefix would issue 16-byte
+// accesses at 2-byte-aligned addresses. The Llama vocab (128256) is
+// 8-divisible, so the hot path is unchanged.
 
 #include "kf_common.h"
 
@@ -24,7 +30,7 @@ __global__ __launch_bounds__(CE_BLOCK) void kf_ce_fwd_kernel(
     const int64_t* __restrict__ targets, int64_t T, int64_t V,
     int64_t ignore_index) {
   __shared__ float scratch[CE_BLOCK / KF_WAVE];
-  const int64_t nvec = V / CE_VEC;
+  const int64_t nvec = (V % CE_VEC == 0) ? V / CE_VEC : 0;
   for (int64_t t = blockIdx.x; t < T; t += gridDim.x) {
     const unsigned short* row = logits + t * V;
     float mx = -INFINITY, sm = 0.f;
@@ -37,7 +43,7 @@ __global__ __launch_bounds__(CE_BLOCK) void kf_ce_fwd_kernel(
         sm += __expf(f - mx);
       }
     }
-    // tail (V % 8) — Llama vocab 128256 is 8-divisible, generic anyway
+    // scalar loop: the whole row when V % 8 != 0 (nvec == 0), else empty
     for (int64_t i = nvec * CE_VEC + threadIdx.x; i < V; i += CE_BLOCK) {
       float f = kf_bf16_to_f32(row[i]);
       if (f > mx) { sm *= __expf(mx - f); mx = f; }
@@ -63,7 +69,7 @@ __global__ __launch_bounds__(CE_BLOCK) void kf_ce_bwd_kernel(
     const int64_t* __restrict__ targets, const float* __restrict__ scale_ptr,
     int64_t T, int64_t V, int64_t ignore_index) {
   const float scale = scale_ptr[0];
-  const int64_t nvec = V / CE_VEC;
+  const int64_t nvec = (V % CE_VEC == 0) ? V / CE_VEC : 0;
   for (int64_t t = blockIdx.x; t < T; t += gridDim.x) {
     const unsigned short* row = logits + t * V;
     unsigned short* drow = dlogits + t * V;

@@ -1,0 +1,338 @@
+"""Parity-test helpers: per-row error metrics, fp32 oracles that return every
+output of an op, and a bf16-emulated attention that sets the per-row bound.
+
+Plain torch, CPU only, importable without a GPU. The oracles are thin
+autograd wrappers over `ops/reference.py` (the single source of the math);
+only `emulated()` spells the attention math out, because it has to round
+every intermediate to bf16.
+
+Why a per-row metric: a whole-tensor Frobenius ratio averages a wrong row or
+a wrong 32-row sub-tile over the whole tensor, so a dropped store or an
+off-by-one mask in one tile passes a 2e-2 bound (see
+tests/test_parity_metric_cpu.py). `row_err` is the worst row instead.
+
+Per-row bounds
+  * attention (o, dq, dk, dv): 3 x row_err(emulated, oracle) on the case's own
+    seeded inputs. `emulated()` holds scores, P, dP, dS and all outputs in
+    bf16, which rounds strictly more than the kernels (fp32 accumulators, fp32
+    softmax statistics), so a correct kernel sits below 1 x; the factor 3
+    covers a different summation order. It is derived from the reference
+    alone, never from a kernel's output.
+  * elementwise / row kernels (rope, norms, swiglu, CE grads, adamw p16): the
+    op's whole-tensor bound from tests/test_ops_gpu.py, applied per row. A
+    correctly bf16-rounded row sits at 2^-9 ~ 0.002, a wrong row near 1.
+"""
+from __future__ import annotations
+
+from typing import Dict, NamedTuple, Optional, Tuple
+
+import torch
+
+from . import reference as R
+
+__all__ = [
+    "row_err", "col_err", "rel_err", "attention_inputs", "attention_oracle",
+    "emulated", "attention_case", "AttnCase", "rope_oracle",
+    "rms_norm_oracle", "layer_norm_oracle", "swiglu_oracle",
+    "cross_entropy_oracle", "adamw_oracle", "decode_oracle",
+    "linear_residual_oracle",
+]
+
+
+# ------------------------------------------------------------------ metrics
+
+def _f32(t: torch.Tensor) -> torch.Tensor:
+    return t.detach().float().cpu()
+
+
+def rel_err(got: torch.Tensor, ref: torch.Tensor) -> float:
+    """Whole-tensor Frobenius ratio (the metric of tests/test_ops_gpu.py)."""
+    got, ref = _f32(got), _f32(ref)
+    return ((got - ref).norm() / (ref.norm() + 1e-12)).item()
+
+
+def row_err(got: torch.Tensor, ref: torch.Tensor) -> float:
+    """max_r ||got_r - ref_r|| / max(||ref_r||, rms), the last dim being the
+    row and rms = sqrt(mean_r ||ref_r||^2).
+
+    The rms floor keeps rows that are (near) zero in the oracle from
+    dominating: causal dq row 0 is exactly 0 in fp32 and a few bf16 ulps in
+    any kernel. NaN anywhere in `got` gives nan (which fails every `<`)."""
+    got, ref = _f32(got), _f32(ref)
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    got = got.reshape(-1, got.shape[-1])
+    ref = ref.reshape(-1, ref.shape[-1])
+    rn = ref.norm(dim=1)
+    rms = rn.pow(2).mean().sqrt()
+    den = torch.maximum(rn, rms).clamp_min(1e-30)
+    e = (got - ref).norm(dim=1) / den
+    if torch.isnan(e).any():
+        return float("nan")
+    return e.max().item()
+
+
+def col_err(got: torch.Tensor, ref: torch.Tensor) -> float:
+    """row_err over the other axis: every column of the [-1, last] view is one
+    "row". For a dW/dB vector [cols] each element is its own row."""
+    got, ref = _f32(got), _f32(ref)
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    return row_err(got.reshape(-1, got.shape[-1]).t(),
+                   ref.reshape(-1, ref.shape[-1]).t())
+
+
+# ---------------------------------------------------------------- attention
+
+def attention_inputs(B: int, S: int, Hq: int, Hkv: int, D: int = 128,
+                     seed: int = 1234):
+    """Seeded bf16 randn (q, k, v, dout) in bshd, built on the CPU."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    q = torch.randn(B, S, Hq, D, generator=g).bfloat16()
+    k = torch.randn(B, S, Hkv, D, generator=g).bfloat16()
+    v = torch.randn(B, S, Hkv, D, generator=g).bfloat16()
+    dout = torch.randn(B, S, Hq, D, generator=g).bfloat16()
+    return q, k, v, dout
+
+
+def _rope_rows(x, cos, sin, pos_offset, positions):
+    """reference.rope_apply with one base position for the batch, or one per
+    batch row (`positions`, int64 [B])."""
+    if positions is None:
+        return R.rope_apply(x, cos, sin, pos_offset)
+    return torch.cat([R.rope_apply(x[i:i + 1], cos, sin, int(positions[i]))
+                      for i in range(x.shape[0])])
+
+
+def _lse(q, k, scale, causal):
+    """logsumexp of the fp32 scores, [B, Hq, S]; q/k bshd (k already sliced
+    and rotated)."""
+    g = q.shape[2] // k.shape[2]
+    kk = k.float().repeat_interleave(g, dim=2)
+    s = torch.einsum("bqhd,bkhd->bhqk", q.float(), kk) * scale
+    if causal:
+        Sq, Sk = s.shape[-2:]
+        mask = torch.ones(Sq, Sk, dtype=torch.bool).tril(Sk - Sq)
+        s = s.masked_fill(~mask, float("-inf"))
+    return torch.logsumexp(s, dim=-1)
+
+
+def attention_oracle(q, k, v, dout, causal: bool, scale: Optional[float] = None,
+                     kv_len: Optional[int] = None, cos=None, sin=None,
+                     pos_offset: int = 0, positions=None):
+    """fp32 oracle, bshd: (o, lse, dq, dk, dv) by autograd through
+    reference.rope_apply (if cos/sin given) and reference.sdpa. k/v are sliced
+    to kv_len, so dk/dv rows past it are zero. Gradients are with respect to
+    the un-rotated q and k."""
+    D = q.shape[-1]
+    if scale is None:
+        scale = D ** -0.5
+    qr, kr, vr = (_f32(t).clone().requires_grad_(True) for t in (q, k, v))
+    q2, k2 = qr, kr
+    if cos is not None:
+        q2 = _rope_rows(qr, cos, sin, pos_offset, positions)
+        k2 = _rope_rows(kr, cos, sin, pos_offset, positions)
+    v2 = vr
+    if kv_len is not None:
+        k2, v2 = k2[:, :kv_len], v2[:, :kv_len]
+    o = R.sdpa(q2.transpose(1, 2), k2.transpose(1, 2), v2.transpose(1, 2),
+               causal=causal, scale=scale).transpose(1, 2)
+    o.backward(_f32(dout))
+    with torch.no_grad():
+        lse = _lse(q2, k2, scale, causal)
+    return o.detach(), lse, qr.grad, kr.grad, vr.grad
+
+
+def _bf(t: torch.Tensor) -> torch.Tensor:
+    """Round to bf16 and back: 'held in bf16'."""
+    return t.bfloat16().float()
+
+
+def emulated(q, k, v, dout, causal: bool, scale: Optional[float] = None,
+             kv_len: Optional[int] = None, cos=None, sin=None,
+             pos_offset: int = 0, positions=None):
+    """The same attention, forward and backward, with every intermediate
+    rounded to bf16: rotated q/k, scores, P, o, dP, delta, dS, per-head dk/dv
+    and all outputs. Returns (o, lse, dq, dk, dv) as fp32 tensors holding
+    bf16 values (lse from the bf16 scores, fp32). A correct kernel rounds
+    only P, dS and the outputs and accumulates in fp32, so this is an upper
+    envelope of honest bf16 error, not a model of any one kernel."""
+    B, S, Hq, D = q.shape
+    Hkv = k.shape[2]
+    g = Hq // Hkv
+    if scale is None:
+        scale = D ** -0.5
+    q2, k2 = q.bfloat16(), k.bfloat16()
+    if cos is not None:  # rope_apply computes in fp32 and rounds to x.dtype
+        q2 = _rope_rows(q2, cos, sin, pos_offset, positions)
+        k2 = _rope_rows(k2, cos, sin, pos_offset, positions)
+    L = S if kv_len is None else kv_len
+    qf = q2.float().transpose(1, 2)                       # [B,Hq,S,D]
+    kf = k2.float()[:, :L].transpose(1, 2).repeat_interleave(g, dim=1)
+    vf = v.bfloat16().float()[:, :L].transpose(1, 2).repeat_interleave(
+        g, dim=1)
+    dof = dout.bfloat16().float().transpose(1, 2)
+    s = _bf(torch.einsum("bhqd,bhkd->bhqk", qf, kf) * scale)
+    if causal:
+        mask = torch.ones(S, L, dtype=torch.bool).tril(L - S)
+        s = s.masked_fill(~mask, float("-inf"))
+    lse = torch.logsumexp(s, dim=-1)
+    p = _bf(torch.softmax(s, dim=-1))
+    o = _bf(torch.einsum("bhqk,bhkd->bhqd", p, vf))
+    dp = _bf(torch.einsum("bhqd,bhkd->bhqk", dof, vf))
+    delta = _bf((dof * o).sum(dim=-1, keepdim=True))
+    ds = _bf(p * (dp - delta))
+    dq = _bf(torch.einsum("bhqk,bhkd->bhqd", ds, kf) * scale)
+    dk = _bf(torch.einsum("bhqk,bhqd->bhkd", ds, qf) * scale)
+    dv = _bf(torch.einsum("bhqk,bhqd->bhkd", p, dof))
+    # GQA: the group's per-head bf16 partials are summed, then rounded again
+    dk = _bf(dk.view(B, Hkv, g, L, D).sum(dim=2))
+    dv = _bf(dv.view(B, Hkv, g, L, D).sum(dim=2))
+    dq = dq.transpose(1, 2)
+    dk_full = torch.zeros(B, S, Hkv, D)
+    dv_full = torch.zeros(B, S, Hkv, D)
+    dk_full[:, :L] = dk.transpose(1, 2)
+    dv_full[:, :L] = dv.transpose(1, 2)
+    if cos is not None:
+        # adjoint of the rotation = rotation by -angle, on the bf16 grads
+        dq = _rope_rows(dq.bfloat16(), cos, -sin, pos_offset,
+                        positions).float()
+        dk_full = _rope_rows(dk_full.bfloat16(), cos, -sin, pos_offset,
+                             positions).float()
+    return o.transpose(1, 2).contiguous(), lse, dq.contiguous(), dk_full, \
+        dv_full
+
+
+class AttnCase(NamedTuple):
+    inputs: Tuple[torch.Tensor, ...]   # q, k, v, dout (bf16, CPU, un-rotated)
+    oracle: Dict[str, torch.Tensor]    # o, lse, dq, dk, dv (fp32)
+    emu_err: Dict[str, float]          # row_err(emulated, oracle) per output
+    bound: Dict[str, float]            # 3 x emu_err
+
+
+_ATTN_CACHE: Dict[tuple, AttnCase] = {}
+ROW_BOUND_FACTOR = 3.0
+_OUTS = ("o", "lse", "dq", "dk", "dv")
+
+
+def attention_case(B: int, S: int, Hq: int, Hkv: int, causal: bool,
+                   D: int = 128, seed: int = 1234,
+                   kv_len: Optional[int] = None, rope_len: Optional[int] = None,
+                   pos_offset: int = 0,
+                   positions: Optional[Tuple[int, ...]] = None) -> AttnCase:
+    """Inputs, fp32 oracle and per-row bounds of one attention case, computed
+    once per argument tuple. rope_len: length of the cos/sin table (None = no
+    RoPE); `positions` a tuple of per-batch base positions."""
+    key = (B, S, Hq, Hkv, causal, D, seed, kv_len, rope_len, pos_offset,
+           positions)
+    if key in _ATTN_CACHE:
+        return _ATTN_CACHE[key]
+    inputs = attention_inputs(B, S, Hq, Hkv, D, seed)
+    kw = dict(kv_len=kv_len)
+    if rope_len is not None:
+        cos, sin = R.rope_cos_sin(rope_len, D)
+        kw.update(cos=cos, sin=sin, pos_offset=pos_offset,
+                  positions=None if positions is None
+                  else torch.tensor(positions))
+    oracle = dict(zip(_OUTS, attention_oracle(*inputs, causal, **kw)))
+    emu = dict(zip(_OUTS, emulated(*inputs, causal, **kw)))
+    emu_err = {n: row_err(emu[n], oracle[n]) for n in ("o", "dq", "dk", "dv")}
+    bound = {n: ROW_BOUND_FACTOR * e for n, e in emu_err.items()}
+    _ATTN_CACHE[key] = AttnCase(inputs, oracle, emu_err, bound)
+    return _ATTN_CACHE[key]
+
+
+# ------------------------------------------------- row / elementwise oracles
+
+def rope_oracle(q, k, cos, sin, pos_offset: int = 0, positions=None,
+                dq2=None, dk2=None):
+    """(q2, k2[, dq, dk]): reference.rope_apply in fp32, per batch row when
+    `positions` is given; with upstream grads dq2/dk2 also the input grads."""
+    qr, kr = (_f32(t).clone().requires_grad_(True) for t in (q, k))
+    q2 = _rope_rows(qr, cos, sin, pos_offset, positions)
+    k2 = _rope_rows(kr, cos, sin, pos_offset, positions)
+    if dq2 is None:
+        return q2.detach(), k2.detach()
+    gq, gk = torch.autograd.grad(
+        (q2 * _f32(dq2)).sum() + (k2 * _f32(dk2)).sum(), [qr, kr])
+    return q2.detach(), k2.detach(), gq, gk
+
+
+def rms_norm_oracle(x, w, dy, eps: float = 1e-5):
+    """(y, dx, dw) of reference.rms_norm in fp32."""
+    xr, wr = (_f32(t).clone().requires_grad_(True) for t in (x, w))
+    y = R.rms_norm(xr, wr, eps)
+    y.backward(_f32(dy))
+    return y.detach(), xr.grad, wr.grad
+
+
+def layer_norm_oracle(x, w, b, dy, eps: float = 1e-5):
+    """(y, dx, dw, db) of reference.layer_norm in fp32."""
+    xr, wr, br = (_f32(t).clone().requires_grad_(True) for t in (x, w, b))
+    y = R.layer_norm(xr, wr, br, eps)
+    y.backward(_f32(dy))
+    return y.detach(), xr.grad, wr.grad, br.grad
+
+
+def swiglu_oracle(h, dy):
+    """(y, dh) of silu(gate) * up, h = [gate ++ up], in fp32."""
+    hr = _f32(h).clone().requires_grad_(True)
+    g, u = hr.chunk(2, dim=-1)
+    y = torch.nn.functional.silu(g) * u
+    y.backward(_f32(dy))
+    return y.detach(), hr.grad
+
+
+def cross_entropy_oracle(logits, targets, ignore_index: int = -100,
+                         grad_out: float = 1.0):
+    """(loss, dlogits) of reference.softmax_cross_entropy in fp32, with the
+    ops wrapper's all-ignored semantics: loss 0 and zero grad (inv_valid = 0),
+    not F.cross_entropy's NaN."""
+    lr = _f32(logits).clone().requires_grad_(True)
+    tg = targets.detach().cpu()
+    if not bool((tg != ignore_index).any()):
+        return torch.zeros(()), torch.zeros_like(lr)
+    loss = R.softmax_cross_entropy(lr, tg, ignore_index)
+    loss.backward(torch.tensor(float(grad_out)))
+    return loss.detach(), lr.grad
+
+
+def adamw_oracle(p32, grads, wd_mask, lr, beta1, beta2, eps, weight_decay):
+    """(p32, m, v) after len(grads) steps of reference.adamw_step from zero
+    moments. A {0,1} wd_mask selects, per element, between a run with the
+    decay and a run without it (the update is elementwise and m, v do not
+    depend on the decay)."""
+    def run(wd):
+        p = _f32(p32).clone()
+        m, v = torch.zeros_like(p), torch.zeros_like(p)
+        for step, g in enumerate(grads, 1):
+            R.adamw_step(p, _f32(g), m, v, lr, beta1, beta2, eps, wd, step)
+        return p, m, v
+    p, m, v = run(weight_decay)
+    if wd_mask is not None:
+        p0, _, _ = run(0.0)
+        p = torch.where(_f32(wd_mask) != 0, p, p0)
+    return p, m, v
+
+
+def decode_oracle(q, kcache, vcache, slots, lens, scale=None):
+    """[N, Hq, D] fp32: per-sequence reference.sdpa over the cached prefix;
+    a sequence with len == 0 attends nothing and gives a zero row."""
+    N, Hq, D = q.shape
+    if scale is None:
+        scale = D ** -0.5
+    out = torch.zeros(N, Hq, D)
+    for i in range(N):
+        L, s = int(lens[i]), int(slots[i])
+        if L == 0:
+            continue
+        o = R.sdpa(_f32(q[i]).view(1, 1, Hq, D).transpose(1, 2),
+                   _f32(kcache[s, :L]).unsqueeze(0).transpose(1, 2),
+                   _f32(vcache[s, :L]).unsqueeze(0).transpose(1, 2),
+                   causal=False, scale=scale)
+        out[i] = o.transpose(1, 2).reshape(Hq, D)
+    return out
+
+
+def linear_residual_oracle(x, w, residual=None):
+    """fp32 x @ w^T (+ residual)."""
+    y = torch.nn.functional.linear(_f32(x), _f32(w))
+    return y if residual is None else y + _f32(residual)

@@ -1,0 +1,334 @@
+"""D = 128 attention: every dispatch branch against the fp32 oracle, under the
+whole-tensor bounds AND the per-row bound of kubeflow_amd/ops/testing.py.
+
+Inputs are seeded bf16 randn built on the CPU (testing.attention_inputs); the
+oracle is autograd through reference.rope_apply + reference.sdpa in fp32.
+Every case asserts, for o, dq, dk, dv:
+  * whole-tensor rel. error < 2e-2 (o) / 4e-2 (grads): test_ops_gpu.py's;
+  * per-row error < 3 x the all-bf16 emulation's per-row error on the same
+    inputs (computed on the CPU from the reference alone);
+and lse against logsumexp of the fp32 scores, atol 1e-2 (the D = 64 test's
+bound). Entry points called directly get NaN-filled output buffers, so a row
+that is never stored fails.
+
+Branches (kf_attn_fwd / kf_attn_bwd_rope dispatch on S % 256):
+  4-wave kf_attn_fwd_kernel + kf_attn_dq_kernel + kf_attn_dkv_kernel for
+  S % 256 != 0, with the kf_rope(backward=1) tail when tables are passed;
+  8-wave fwd4 + dq8 + dkv8f for S % 256 == 0, rotation in the epilogues;
+  KF_ATTN_IMPL=3 (fwd8) and 5 (fwd5) forward bisection paths, each in a fresh
+  child process because the switch is cached in a C static.
+"""
+import ctypes
+import json
+import os
+import subprocess
+import sys
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from kubeflow_amd import ops
+from kubeflow_amd.ops import testing as T
+
+D = 128
+FWD_BOUND = 2e-2   # test_attention_fwd's bound
+BWD_BOUND = 4e-2   # test_attention_bwd's bound
+LSE_ATOL = 1e-2    # test_attn_d64_gpu.py::test_direct_fwd_lse's bound
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# name -> (B, S, Hq, Hkv, causal)
+PLAIN_CASES = {
+    # ---- 4-wave path (S % 256 != 0) ----
+    # one q tile per head, two 64-row kv tiles, no mask, g = 1, batch stride
+    "w4_one_tile_noncausal": (2, 128, 4, 4, False),
+    # one q tile: diagonal + skipped kv tiles; g = 4 head loop in dkv
+    "w4_one_tile_causal_gqa4": (1, 128, 4, 1, True),
+    # three q tiles: diagonal + full + skipped kv tiles, g = 2
+    "w4_three_tiles_causal": (1, 384, 4, 2, True),
+    # three q tiles, every kv tile full, batch stride
+    "w4_three_tiles_noncausal": (2, 384, 2, 2, False),
+    # ---- 8-wave path (S % 256 == 0): fwd4, dq8, dkv8f ----
+    # two 256-row blocks, g = 4, batch stride, kt-major block decode
+    "w8_two_blocks_causal_gqa4": (2, 512, 4, 1, True),
+    # g = 1, no mask path
+    "w8_noncausal": (1, 512, 2, 2, False),
+    # three 256-row blocks: LPT order with an odd block count
+    "w8_three_blocks_causal": (1, 768, 4, 2, True),
+}
+# 4-wave path through ops.flash_attention's zero-pad (S = 100 -> 128); the
+# outputs are sliced back to 100 rows and padded rows' grads never returned
+PAD_CASE = (1, 100, 2, 2, True)
+
+# strided fused-qkv + RoPE at pos_offset 77, table of S + 128 rows, causal:
+# name -> (B, S, Hq, Hkv)
+ROPE_OFFSET = 77
+ROPE_CASES = {
+    "rope_w4_tail": (2, 384, 4, 2),      # 4-wave kernels + kf_rope(backward=1)
+    "rope_w8_epilogue": (2, 512, 4, 2),  # dq8 / dkv8f store epilogues
+}
+# ops.fused_qkv_attention (offset 0, table of S rows): name -> (B, S, Hq, Hkv)
+FUSED_CASES = {
+    "fused_qkv_s128": (2, 128, 4, 2),    # 4-wave, one q tile
+    "fused_qkv_s384": (1, 384, 4, 2),    # 4-wave, three q tiles
+}
+# forward bisection children: (B, S, Hq, Hkv, causal), both S % 256 == 0
+IMPL_CASES = [(1, 512, 4, 2, True), (1, 256, 2, 2, False)]
+
+_cache = {}
+
+
+def _p(t, off=0):
+    return ctypes.c_void_p(t.data_ptr() + off * t.element_size())
+
+
+def _fp(t):
+    return ctypes.cast(t.data_ptr(), ctypes.POINTER(ctypes.c_float))
+
+
+def _null_i64():
+    return ctypes.cast(0, ctypes.POINTER(ctypes.c_int64))
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _ok(err, name):
+    assert err == 0, f"{name} failed with hipError_t={err}"
+
+
+def _nan(*shape, dtype=torch.bfloat16):
+    return torch.full(shape, float("nan"), dtype=dtype,
+                      device=torch.device("cuda", 0))
+
+
+def _check(name, got, case, outs=("o", "dq", "dk", "dv"), lse=True):
+    """Both metrics on every output; prints the figures before asserting."""
+    rows = []
+    for out in outs:
+        whole = T.rel_err(got[out], case.oracle[out])
+        row = T.row_err(got[out], case.oracle[out])
+        rows.append((out, whole, row))
+        print(f"PARITY {name} {out} whole={whole:.5f} row={row:.5f} "
+              f"emu_row={case.emu_err[out]:.5f} bound={case.bound[out]:.5f}")
+    if lse:
+        d = (got["lse"].float().cpu() - case.oracle["lse"]).abs().max().item()
+        print(f"PARITY {name} lse maxabs={d:.6f}")
+    for out, whole, row in rows:
+        assert got[out].shape == case.oracle[out].shape, out
+        assert whole < (FWD_BOUND if out == "o" else BWD_BOUND), (out, whole)
+        assert row < case.bound[out], (out, row, case.bound[out])
+    if lse:
+        assert torch.allclose(got["lse"].float().cpu(), case.oracle["lse"],
+                              atol=LSE_ATOL), d
+
+
+# ------------------------------------------------------- plain bshd cases
+
+def _plain(name):
+    """kf_attn_fwd + kf_attn_bwd on contiguous bshd tensors, run once."""
+    if name in _cache:
+        return _cache[name]
+    from kubeflow_amd.ops import _backend
+    lib = _backend.require()
+    B, S, Hq, Hkv, causal = PLAIN_CASES[name]
+    case = T.attention_case(B, S, Hq, Hkv, causal)
+    dev = torch.device("cuda", 0)
+    scale = D ** -0.5
+    q, k, v, dout = (t.to(dev) for t in case.inputs)
+    o = _nan(B, S, Hq, D)
+    lse = _nan(B, Hq, S, dtype=torch.float32)
+    _ok(lib.kf_attn_fwd(_p(o), _fp(lse), _p(q), _p(k), _p(v), B, S, Hq, Hkv,
+                        D, 0, 0, scale, int(causal), _stream()), "attn_fwd")
+    dq, dk, dv = _nan(B, S, Hq, D), _nan(B, S, Hkv, D), _nan(B, S, Hkv, D)
+    delta = _nan(B, Hq, S, dtype=torch.float32)
+    _ok(lib.kf_attn_bwd(_p(dq), _p(dk), _p(dv), _p(dout), _p(q), _p(k), _p(v),
+                        _p(o), _fp(lse), _fp(delta), B, S, Hq, Hkv, D, 0, 0,
+                        0, 0, scale, int(causal), _stream()), "attn_bwd")
+    torch.cuda.synchronize()
+    got = dict(o=o.cpu(), lse=lse.cpu(), dq=dq.cpu(), dk=dk.cpu(),
+               dv=dv.cpu())
+    _cache[name] = (got, case)
+    return _cache[name]
+
+
+@pytest.mark.parametrize("name", list(PLAIN_CASES))
+def test_fwd_bwd_both_metrics(name):
+    got, case = _plain(name)
+    _check(name, got, case)
+
+
+def _saved_lse(o):
+    """lse saved by the autograd Function that produced o (walks past the
+    pad slice)."""
+    fn = o.grad_fn
+    while not hasattr(fn, "saved_tensors"):
+        fn = fn.next_functions[0][0]
+    return fn.saved_tensors[4]
+
+
+def test_pad_path_both_metrics():
+    """S = 100 causal through ops.flash_attention: zero-padded to 128 (4-wave
+    path), sliced back; the padded key rows are causally masked for every
+    real query, so the result is exact."""
+    B, S, Hq, Hkv, causal = PAD_CASE
+    case = T.attention_case(B, S, Hq, Hkv, causal)
+    dev = torch.device("cuda", 0)
+    q, k, v, dout = (t.to(dev) for t in case.inputs)
+    qg, kg, vg = (t.requires_grad_(True) for t in (q, k, v))
+    o = ops.flash_attention(qg, kg, vg, causal=True)
+    assert o.shape == (B, S, Hq, D)
+    lse = _saved_lse(o)[:, :, :S]
+    o.backward(dout)
+    torch.cuda.synchronize()
+    got = dict(o=o.detach().cpu(), lse=lse.cpu(), dq=qg.grad.cpu(),
+               dk=kg.grad.cpu(), dv=vg.grad.cpu())
+    _check("w4_pad_s100_causal", got, case)
+
+
+def test_pad_path_non_causal_raises():
+    dev = torch.device("cuda", 0)
+    q = torch.zeros(1, 100, 2, D, device=dev, dtype=torch.bfloat16)
+    with pytest.raises(ValueError, match="seq_len % 128 == 0"):
+        ops.flash_attention(q, q, q, causal=False)
+
+
+# ------------------------------------------------- RoPE adjoint, pos_offset
+
+def _rope(name):
+    """kf_rope(pos_offset) -> kf_attn_fwd -> kf_attn_bwd_rope(pos_offset) on
+    the strided fused-qkv layout, run once."""
+    if name in _cache:
+        return _cache[name]
+    from kubeflow_amd.ops import _backend
+    lib = _backend.require()
+    B, S, Hq, Hkv = ROPE_CASES[name]
+    case = T.attention_case(B, S, Hq, Hkv, True, rope_len=S + 128,
+                            pos_offset=ROPE_OFFSET)
+    dev = torch.device("cuda", 0)
+    scale = D ** -0.5
+    ts = (Hq + 2 * Hkv) * D  # token stride of q, k, v and of dq, dk, dv
+    ko, vo = Hq * D, (Hq + Hkv) * D
+    q, k, v, dout = case.inputs
+    qkv = torch.cat([q.reshape(B, S, -1), k.reshape(B, S, -1),
+                     v.reshape(B, S, -1)], dim=-1).to(dev)
+    dout = dout.reshape(B, S, Hq * D).to(dev)
+    # the oracle's own table, so kernel and oracle rotate by the same fp32
+    cos, sin = (t.to(dev) for t in ops.rope_cos_sin(S + 128, D))
+    # forward rotation in place, as the fused forward does, at the offset
+    _ok(lib.kf_rope(_p(qkv), _p(qkv, ko), _fp(cos), _fp(sin), _null_i64(), B,
+                    S, Hq, Hkv, D, ts, ts, ROPE_OFFSET, 0, _stream()),
+        "rope_fwd")
+    o = _nan(B, S, Hq * D)
+    lse = _nan(B, Hq, S, dtype=torch.float32)
+    _ok(lib.kf_attn_fwd(_p(o), _fp(lse), _p(qkv), _p(qkv, ko), _p(qkv, vo),
+                        B, S, Hq, Hkv, D, ts, ts, scale, 1, _stream()),
+        "attn_fwd")
+    dqkv = _nan(B, S, ts)
+    delta = _nan(B, Hq, S, dtype=torch.float32)
+    _ok(lib.kf_attn_bwd_rope(
+        _p(dqkv), _p(dqkv, ko), _p(dqkv, vo), _p(dout), _p(qkv), _p(qkv, ko),
+        _p(qkv, vo), _p(o), _fp(lse), _fp(delta), B, S, Hq, Hkv, D, ts, ts,
+        ts, ts, scale, 1, _fp(cos), _fp(sin), ROPE_OFFSET, _stream()),
+        "attn_bwd_rope")
+    torch.cuda.synchronize()
+    dq, dk, dv = dqkv.cpu().split([Hq * D, Hkv * D, Hkv * D], dim=-1)
+    got = dict(o=o.cpu().view(B, S, Hq, D), lse=lse.cpu(),
+               dq=dq.reshape(B, S, Hq, D), dk=dk.reshape(B, S, Hkv, D),
+               dv=dv.reshape(B, S, Hkv, D))
+    _cache[name] = (got, case)
+    return _cache[name]
+
+
+@pytest.mark.parametrize("name", list(ROPE_CASES))
+def test_rope_adjoint_pos_offset_both_metrics(name):
+    got, case = _rope(name)
+    _check(name, got, case)
+
+
+@pytest.mark.parametrize("name", list(FUSED_CASES))
+def test_fused_qkv_attention_both_metrics(name):
+    """ops.fused_qkv_attention forward and dqkv on the 4-wave path (in-place
+    kf_rope, strided kf_attn_fwd, kf_attn_bwd_rope with the kf_rope tail)."""
+    B, S, Hq, Hkv = FUSED_CASES[name]
+    case = T.attention_case(B, S, Hq, Hkv, True, rope_len=S, pos_offset=0)
+    dev = torch.device("cuda", 0)
+    q, k, v, dout = case.inputs
+    qkv = torch.cat([q.reshape(B, S, -1), k.reshape(B, S, -1),
+                     v.reshape(B, S, -1)], dim=-1).to(dev).requires_grad_(True)
+    cos, sin = (t.to(dev) for t in ops.rope_cos_sin(S, D))
+    o = ops.fused_qkv_attention(qkv, cos, sin, Hq, Hkv, D)
+    lse = _saved_lse(o)
+    o.backward(dout.reshape(B, S, Hq * D).to(dev))
+    torch.cuda.synchronize()
+    dq, dk, dv = qkv.grad.cpu().split([Hq * D, Hkv * D, Hkv * D], dim=-1)
+    got = dict(o=o.detach().cpu().view(B, S, Hq, D), lse=lse.cpu(),
+               dq=dq.reshape(B, S, Hq, D), dk=dk.reshape(B, S, Hkv, D),
+               dv=dv.reshape(B, S, Hkv, D))
+    _check(name, got, case)
+
+
+# ------------------------------------------------ forward bisection paths
+
+_CHILD = r"""
+import ctypes, json, sys
+import torch
+from kubeflow_amd.ops import _backend
+from kubeflow_amd.ops import testing as T
+
+lib = _backend.require()
+dev = torch.device("cuda", 0)
+D = 128
+out = {}
+for B, S, Hq, Hkv, causal in json.loads(sys.argv[2]):
+    q, k, v, _ = (t.to(dev) for t in T.attention_inputs(B, S, Hq, Hkv))
+    o = torch.full((B, S, Hq, D), float("nan"), dtype=torch.bfloat16,
+                   device=dev)
+    lse = torch.full((B, Hq, S), float("nan"), dtype=torch.float32,
+                     device=dev)
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())
+    err = lib.kf_attn_fwd(
+        vp(o), ctypes.cast(lse.data_ptr(), ctypes.POINTER(ctypes.c_float)),
+        vp(q), vp(k), vp(v), B, S, Hq, Hkv, D, 0, 0, D ** -0.5, int(causal),
+        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if err:
+        sys.exit(f"kf_attn_fwd failed with hipError_t={err}")
+    torch.cuda.synchronize()
+    out[f"{B}_{S}_{Hq}_{Hkv}_{int(causal)}"] = (o.cpu(), lse.cpu())
+torch.save(out, sys.argv[1])
+"""
+
+
+def _impl_child(impl, tmp_path):
+    """One fresh process with KF_ATTN_IMPL=impl; returns its saved outputs. A
+    nonzero exit status fails here and nothing else is started."""
+    path = str(tmp_path / f"impl{impl}.pt")
+    env = dict(os.environ, KF_ATTN_IMPL=str(impl))
+    env.pop("KF_ATTN_V4", None)
+    r = subprocess.run(
+        [sys.executable, "-c", _CHILD, path, json.dumps(IMPL_CASES)],
+        cwd=REPO, env=env, timeout=120, capture_output=True, text=True)
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:],
+                               r.stderr[-2000:])
+    return torch.load(path)
+
+
+def _check_impl(impl, tmp_path):
+    saved = _impl_child(impl, tmp_path)
+    for B, S, Hq, Hkv, causal in IMPL_CASES:
+        o, lse = saved[f"{B}_{S}_{Hq}_{Hkv}_{int(causal)}"]
+        case = T.attention_case(B, S, Hq, Hkv, causal)
+        _check(f"impl{impl}_S{S}_{'causal' if causal else 'noncausal'}",
+               dict(o=o, lse=lse), case, outs=("o",))
+
+
+def test_fwd_impl3_child_process(tmp_path):
+    """KF_ATTN_IMPL=3: the round-1 8-wave kf_attn_fwd8_kernel."""
+    _check_impl(3, tmp_path)
+
+
+def test_fwd_impl5_child_process(tmp_path):
+    """KF_ATTN_IMPL=5: kf_attn_fwd5 (4 waves x 64 q rows, parked)."""
+    _check_impl(5, tmp_path)
