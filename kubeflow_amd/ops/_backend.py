@@ -40,11 +40,12 @@ def try_load():
             _load_error = f"build failed: {e}"
             return None
     try:
-        _lib = ctypes.CDLL(str(_LIB_PATH))
+        lib = ctypes.CDLL(str(_LIB_PATH))
     except OSError as e:  # pragma: no cover
         _load_error = str(e)
         return None
-    _configure(_lib)
+    _configure(lib)  # raises, naming the symbol, if one is missing
+    _lib = lib
     return _lib
 
 
@@ -60,93 +61,83 @@ def require():
     return lib
 
 
+# The C ABI of libkfops.so as data: entry point -> argtypes, one entry per
+# prototype in csrc/kf_ops.h (tests/test_ops_abi.py checks the two against
+# each other). Every entry point returns hipError_t as int, except the two
+# *_nparts helpers, which return a count as int64.
+_P, _F = ctypes.c_void_p, ctypes.c_float
+_I64, _I32 = ctypes.c_int64, ctypes.c_int
+_FP = ctypes.POINTER(ctypes.c_float)
+_PI64 = ctypes.POINTER(ctypes.c_int64)
+_PI32 = ctypes.POINTER(ctypes.c_int32)
+
+# dq, q, k, v, dout, lse, delta, B, S, Hq, Hkv, qts, kts, dqts, scale, causal
+_DQ8 = [_P] * 5 + [_FP, _FP] + [_I64] * 7 + [_F, _I32]
+_DKV8 = [_P] + _DQ8                 # dk, dv lead instead of dq; dkts for dqts
+_ROPE_TAIL = [_FP, _FP, _I64]       # cos, sin, pos_offset before the stream
+# dq, dk, dv, dout, q, k, v, o, lse, delta, B, S, Hq, Hkv
+_BWD_HEAD = [_P] * 8 + [_FP, _FP] + [_I64] * 4
+# D, qts, kts, dqts, dkts, scale, causal
+_ATTN_BWD = _BWD_HEAD + [_I64] * 5 + [_F, _I32]
+# o, lse, q, k, v, B, S, Hq, Hkv, D, qts, kts, scale, causal, stream
+_ATTN_FWD = [_P, _FP, _P, _P, _P] + [_I64] * 7 + [_F, _I32, _P]
+
+SIGNATURES: dict[str, list] = {
+    "kf_rmsnorm_fwd": [_P, _FP, _P, _P, _I64, _I64, _F, _P],
+    "kf_rmsnorm_bwd_nparts": [_I64],
+    "kf_rmsnorm_bwd": [_P, _P, _FP, _P, _P, _P, _FP, _I64, _I64, _P],
+    "kf_layernorm_fwd": [_P, _FP, _FP, _P, _P, _P, _I64, _I64, _F, _P],
+    "kf_layernorm_bwd_nparts": [_I64],
+    "kf_layernorm_bwd": [_P, _P, _P, _FP, _P, _P, _P, _FP, _FP, _I64, _I64,
+                         _P],
+    "kf_rope": [_P, _P, _FP, _FP, _PI64] + [_I64] * 8 + [_I32, _P],
+    "kf_swiglu_fwd": [_P, _P, _I64, _I64, _P],
+    "kf_swiglu_bwd": [_P, _P, _P, _I64, _I64, _P],
+    "kf_adamw": [_P, _FP, _P, _FP, _FP, _FP, _I64, _F, _F, _F, _F, _F, _I64,
+                 _P],
+    "kf_ce_fwd": [_FP, _FP, _P, _PI64, _I64, _I64, _I64, _P],
+    "kf_ce_bwd": [_P, _P, _FP, _PI64, _FP, _I64, _I64, _I64, _P],
+    "kf_skinny_gemm": [_P, _P, _P, _P, _FP, _F] + [_I64] * 7 + [_P],
+    "kf_skinny_gemm_q8": [_P, _P, _P, _FP, _P, _FP, _F] + [_I64] * 7 + [_P],
+    "kf_kv_store": [_P] * 6 + [_I64, _I64, _I64, _P],
+    "kf_decode_rope_store": [_P, _P, _P, _P, _FP, _FP, _PI32, _P] +
+                            [_I64] * 5 + [_P],
+    "kf_attn_fwd": _ATTN_FWD,
+    "kf_attn_fwd4": _ATTN_FWD,
+    "kf_attn_fwd5": _ATTN_FWD,
+    # ..., B, Sq, Skv, Hq, Hkv, D, qts, kts, scale, qoff, stream
+    "kf_attn_fwd4_rect": [_P, _FP, _P, _P, _P] + [_I64] * 8 + [_F, _I64, _P],
+    # scripts/attn_ablate.py, scripts/probe_tr16.py
+    "kf_attn_fwd4_abl": [_I32] + _ATTN_FWD,
+    "kf_tr16_probe": [_P, _P, _I32, _P],
+    "kf_attn_bwd": _ATTN_BWD + [_P],
+    "kf_attn_bwd_rope": _ATTN_BWD + _ROPE_TAIL + [_P],
+    # per-pass entry points of the 8-wave backward (tests / bisection)
+    "kf_attn_bwd8_dq": _DQ8 + [_P],
+    "kf_attn_bwd8_dq_rope": _DQ8 + _ROPE_TAIL + [_P],
+    "kf_attn_bwd8_dkv": _DKV8 + [_P],
+    "kf_attn_bwd8_dkv_rope": _DKV8 + _ROPE_TAIL + [_P],
+    "kf_attn_bwd8_dkv_fused": _DKV8 + [_P],
+    "kf_attn_bwd8_dkv_fused_rope": _DKV8 + _ROPE_TAIL + [_P],
+    # head-dim-64 family: ..., qts, kts, scale, causal, kv_len, stream
+    "kf_attn64_fwd": [_P, _FP, _P, _P, _P] + [_I64] * 6 + [_F, _I32, _I64,
+                                                           _P],
+    "kf_attn64_bwd": _BWD_HEAD + [_I64, _I64, _F, _I32, _I64, _P],
+    "kf_attn_decode": [_P] * 6 + [_PI32, _PI32] + [_I64] * 6 + [_F, _P],
+}
+_RETURNS_INT64 = ("kf_rmsnorm_bwd_nparts", "kf_layernorm_bwd_nparts")
+
+
 def _configure(lib: ctypes.CDLL) -> None:
-    c = ctypes
-    P, F, I64, I32, FP = c.c_void_p, c.c_float, c.c_int64, c.c_int, c.POINTER(c.c_float)
-    PI64 = c.POINTER(c.c_int64)
-    PI32 = c.POINTER(c.c_int32)
-    lib.kf_rmsnorm_fwd.restype = I32
-    lib.kf_rmsnorm_fwd.argtypes = [P, FP, P, P, I64, I64, F, P]
-    lib.kf_rmsnorm_bwd.restype = I32
-    lib.kf_rmsnorm_bwd.argtypes = [P, P, FP, P, P, P, FP, I64, I64, P]
-    lib.kf_rmsnorm_bwd_nparts.restype = I64
-    lib.kf_rmsnorm_bwd_nparts.argtypes = [I64]
-    lib.kf_rope.restype = I32
-    lib.kf_rope.argtypes = [P, P, FP, FP, PI64, I64, I64, I64, I64, I64, I64, I64, I64, I32, P]
-    lib.kf_adamw.restype = I32
-    lib.kf_adamw.argtypes = [P, FP, P, FP, FP, FP, I64, F, F, F, F, F, I64, P]
-    lib.kf_ce_fwd.restype = I32
-    lib.kf_ce_fwd.argtypes = [FP, FP, P, PI64, I64, I64, I64, P]
-    lib.kf_ce_bwd.restype = I32
-    lib.kf_ce_bwd.argtypes = [P, P, FP, PI64, FP, I64, I64, I64, P]
-    lib.kf_attn_fwd.restype = I32
-    lib.kf_attn_fwd.argtypes = [P, FP, P, P, P, I64, I64, I64, I64, I64, I64, I64, F, I32, P]
-    if hasattr(lib, "kf_skinny_gemm"):
-        lib.kf_skinny_gemm.restype = I32
-        lib.kf_skinny_gemm.argtypes = [P, P, P, P, FP, F, I64, I64, I64,
-                                       I64, I64, I64, I64, P]
-    if hasattr(lib, "kf_skinny_gemm_q8"):
-        lib.kf_skinny_gemm_q8.restype = I32
-        lib.kf_skinny_gemm_q8.argtypes = [P, P, P, FP, P, FP, F, I64,
-                                          I64, I64, I64, I64, I64, I64,
-                                          P]
-    if hasattr(lib, "kf_kv_store"):
-        lib.kf_kv_store.restype = I32
-        lib.kf_kv_store.argtypes = [P, P, P, P, P, P, I64, I64, I64, P]
-    if hasattr(lib, "kf_attn_fwd4_rect"):
-        lib.kf_attn_fwd4_rect.restype = I32
-        lib.kf_attn_fwd4_rect.argtypes = [P, FP, P, P, P, I64, I64, I64,
-                                          I64, I64, I64, I64, I64, F, I64, P]
-    if hasattr(lib, "kf_attn_bwd"):
-        lib.kf_attn_bwd.restype = I32
-        lib.kf_attn_bwd.argtypes = [P, P, P, P, P, P, P, P, FP, FP, I64, I64,
-                                    I64, I64, I64, I64, I64, I64, I64, F, I32,
-                                    P]
-    if hasattr(lib, "kf_attn_bwd_rope"):
-        # kf_attn_bwd's arguments + cos, sin, pos_offset before the stream
-        lib.kf_attn_bwd_rope.restype = I32
-        lib.kf_attn_bwd_rope.argtypes = [P, P, P, P, P, P, P, P, FP, FP, I64,
-                                         I64, I64, I64, I64, I64, I64, I64,
-                                         I64, F, I32, FP, FP, I64, P]
-    # per-pass entry points of the 8-wave backward (tests / bisection);
-    # the *_rope forms add cos, sin, pos_offset before the stream
-    dq8 = [P, P, P, P, P, FP, FP, I64, I64, I64, I64, I64, I64, I64, F, I32]
-    dkv8 = [P] + dq8
-    for name, args in (("kf_attn_bwd8_dq", dq8), ("kf_attn_bwd8_dkv", dkv8),
-                       ("kf_attn_bwd8_dkv_fused", dkv8)):
-        if hasattr(lib, name):
-            getattr(lib, name).restype = I32
-            getattr(lib, name).argtypes = args + [P]
-        if hasattr(lib, name + "_rope"):
-            getattr(lib, name + "_rope").restype = I32
-            getattr(lib, name + "_rope").argtypes = args + [FP, FP, I64, P]
-    # head-dim-64 family (attention_d64.hip): ..., qts, kts, scale, causal,
-    # kv_len, stream
-    if hasattr(lib, "kf_attn64_fwd"):
-        lib.kf_attn64_fwd.restype = I32
-        lib.kf_attn64_fwd.argtypes = [P, FP, P, P, P, I64, I64, I64, I64,
-                                      I64, I64, F, I32, I64, P]
-    if hasattr(lib, "kf_attn64_bwd"):
-        lib.kf_attn64_bwd.restype = I32
-        lib.kf_attn64_bwd.argtypes = [P, P, P, P, P, P, P, P, FP, FP, I64,
-                                      I64, I64, I64, I64, I64, F, I32, I64, P]
-    lib.kf_layernorm_fwd.restype = I32
-    lib.kf_layernorm_fwd.argtypes = [P, FP, FP, P, P, P, I64, I64, F, P]
-    lib.kf_layernorm_bwd.restype = I32
-    lib.kf_layernorm_bwd.argtypes = [P, P, P, FP, P, P, P, FP, FP, I64, I64, P]
-    lib.kf_layernorm_bwd_nparts.restype = I64
-    lib.kf_layernorm_bwd_nparts.argtypes = [I64]
-    lib.kf_swiglu_fwd.restype = I32
-    lib.kf_swiglu_fwd.argtypes = [P, P, I64, I64, P]
-    lib.kf_swiglu_bwd.restype = I32
-    lib.kf_swiglu_bwd.argtypes = [P, P, P, I64, I64, P]
-    lib.kf_attn_decode.restype = I32
-    lib.kf_attn_decode.argtypes = [P, P, P, P, P, P, PI32, PI32, I64, I64,
-                                   I64, I64, I64, I64, F, P]
-    if hasattr(lib, "kf_decode_rope_store"):
-        lib.kf_decode_rope_store.restype = I32
-        lib.kf_decode_rope_store.argtypes = [P, P, P, P, FP, FP, PI32, P,
-                                             I64, I64, I64, I64, I64, P]
+    for name, argtypes in SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise RuntimeError(
+                f"{_LIB_PATH.name} does not export {name}: the library and "
+                "kubeflow_amd/ops/_backend.py disagree") from None
+        fn.restype = _I64 if name in _RETURNS_INT64 else _I32
+        fn.argtypes = argtypes
 
 
 def check(err: int, name: str) -> None:

@@ -13,19 +13,9 @@
 // bank swizzle (guide §6 G4), with the shift adapted to the row byte width.
 // lse layout [B,Hq,S] fp32 comes from kf_attn_fwd.
 
-#include "kf_common.h"
-
-typedef __bf16 kf_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float kf_f32x4 __attribute__((ext_vector_type(4)));
+#include "kf_attn_common.h"
 
 #define AB_D 128
-
-// Swizzled byte offset; xor_mask picks how many row bits fold in (row_bytes
-// 128 -> 7, row_bytes 64 -> 3).
-__device__ __forceinline__ int kf_swz2(int row, int byte_in_row, int row_bytes,
-                                       int xor_mask) {
-  return row * row_bytes + (byte_in_row ^ ((row & xor_mask) << 4));
-}
 
 // ---------------------------------------------------------------- pass 0 --
 __global__ __launch_bounds__(256) void kf_attn_delta2_kernel(
@@ -114,17 +104,17 @@ __global__ __launch_bounds__(256) void kf_attn_dq_kernel(
         const int r = vi >> 4, c8 = vi & 15;
         kf_short8 kv8 =
             *reinterpret_cast<const kf_short8*>(kg + r * kts + c8 * 8);
-        *reinterpret_cast<kf_short8*>(k_lds + kf_swz2(r, c8 * 16, 256, 7)) = kv8;
+        *reinterpret_cast<kf_short8*>(k_lds + kf_swz(r, c8 * 16, 256)) = kv8;
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) {
           const int el = (jj + tid) & 7;
           const int dd = c8 * 8 + el;
           *reinterpret_cast<unsigned short*>(
-              kt_lds + kf_swz2(dd, r * 2, 128, 7)) = (unsigned short)kv8[el];
+              kt_lds + kf_swz(dd, r * 2, 128)) = (unsigned short)kv8[el];
         }
         kf_short8 vv8 =
             *reinterpret_cast<const kf_short8*>(vg + r * kts + c8 * 8);
-        *reinterpret_cast<kf_short8*>(v_lds + kf_swz2(r, c8 * 16, 256, 7)) = vv8;
+        *reinterpret_cast<kf_short8*>(v_lds + kf_swz(r, c8 * 16, 256)) = vv8;
       }
     }
     __syncthreads();
@@ -138,11 +128,11 @@ __global__ __launch_bounds__(256) void kf_attn_dq_kernel(
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) {
         kf_bf16x8 kb = *reinterpret_cast<const kf_bf16x8*>(
-            k_lds + kf_swz2(nt * 16 + l16, kk * 64 + lg * 16, 256, 7));
+            k_lds + kf_swz(nt * 16 + l16, kk * 64 + lg * 16, 256));
         sacc[nt] =
             __builtin_amdgcn_mfma_f32_16x16x32_bf16(qfrag[kk], kb, sacc[nt], 0, 0, 0);
         kf_bf16x8 vb = *reinterpret_cast<const kf_bf16x8*>(
-            v_lds + kf_swz2(nt * 16 + l16, kk * 64 + lg * 16, 256, 7));
+            v_lds + kf_swz(nt * 16 + l16, kk * 64 + lg * 16, 256));
         dpacc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dofrag[kk], vb,
                                                             dpacc[nt], 0, 0, 0);
       }
@@ -160,7 +150,7 @@ __global__ __launch_bounds__(256) void kf_attn_dq_kernel(
                       : __expf(sacc[nt][r] * scale - lse_r[r]);
         float ds = p * (dpacc[nt][r] - dlt_r[r]) * scale;
         *reinterpret_cast<unsigned short*>(
-            ds_lds[w] + kf_swz2(lg * 4 + r, (nt * 16 + l16) * 2, 128, 7)) =
+            ds_lds[w] + kf_swz(lg * 4 + r, (nt * 16 + l16) * 2, 128)) =
             kf_f32_to_bf16(ds);
       }
     }
@@ -171,13 +161,13 @@ __global__ __launch_bounds__(256) void kf_attn_dq_kernel(
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk)
       dsfrag[kk] = *reinterpret_cast<const kf_bf16x8*>(
-          ds_lds[w] + kf_swz2(l16, kk * 64 + lg * 16, 128, 7));
+          ds_lds[w] + kf_swz(l16, kk * 64 + lg * 16, 128));
 #pragma unroll
     for (int nt = 0; nt < 8; ++nt) {
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {
         kf_bf16x8 ktb = *reinterpret_cast<const kf_bf16x8*>(
-            kt_lds + kf_swz2(nt * 16 + l16, kk * 64 + lg * 16, 128, 7));
+            kt_lds + kf_swz(nt * 16 + l16, kk * 64 + lg * 16, 128));
         dqacc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dsfrag[kk], ktb,
                                                             dqacc[nt], 0, 0, 0);
       }
@@ -257,19 +247,19 @@ __global__ __launch_bounds__(256) void kf_attn_dkv_kernel(
           const int r = vi >> 4, c8 = vi & 15;
           kf_short8 q8 =
               *reinterpret_cast<const kf_short8*>(qg + r * qts + c8 * 8);
-          *reinterpret_cast<kf_short8*>(q_lds + kf_swz2(r, c8 * 16, 256, 7)) = q8;
+          *reinterpret_cast<kf_short8*>(q_lds + kf_swz(r, c8 * 16, 256)) = q8;
           kf_short8 do8 =
               *reinterpret_cast<const kf_short8*>(dog + r * dstride + c8 * 8);
-          *reinterpret_cast<kf_short8*>(do_lds + kf_swz2(r, c8 * 16, 256, 7)) =
+          *reinterpret_cast<kf_short8*>(do_lds + kf_swz(r, c8 * 16, 256)) =
               do8;
 #pragma unroll
           for (int jj = 0; jj < 8; ++jj) {
             const int el = (jj + tid) & 7;
             const int dd = c8 * 8 + el;
             *reinterpret_cast<unsigned short*>(
-                qt_lds + kf_swz2(dd, r * 2, 64, 3)) = (unsigned short)q8[el];
+                qt_lds + kf_swz(dd, r * 2, 64)) = (unsigned short)q8[el];
             *reinterpret_cast<unsigned short*>(
-                dot_lds + kf_swz2(dd, r * 2, 64, 3)) = (unsigned short)do8[el];
+                dot_lds + kf_swz(dd, r * 2, 64)) = (unsigned short)do8[el];
           }
         }
       }
@@ -284,11 +274,11 @@ __global__ __launch_bounds__(256) void kf_attn_dkv_kernel(
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
           kf_bf16x8 qb = *reinterpret_cast<const kf_bf16x8*>(
-              q_lds + kf_swz2(nt * 16 + l16, kk * 64 + lg * 16, 256, 7));
+              q_lds + kf_swz(nt * 16 + l16, kk * 64 + lg * 16, 256));
           st[nt] =
               __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfrag[kk], qb, st[nt], 0, 0, 0);
           kf_bf16x8 dob = *reinterpret_cast<const kf_bf16x8*>(
-              do_lds + kf_swz2(nt * 16 + l16, kk * 64 + lg * 16, 256, 7));
+              do_lds + kf_swz(nt * 16 + l16, kk * 64 + lg * 16, 256));
           dpt[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfrag[kk], dob,
                                                             dpt[nt], 0, 0, 0);
         }
@@ -309,10 +299,10 @@ __global__ __launch_bounds__(256) void kf_attn_dkv_kernel(
           float ds = p * (dpt[nt][r] - dlt_c) * scale;
           const int prow = lg * 4 + r;
           *reinterpret_cast<unsigned short*>(
-              pt_lds[w] + kf_swz2(prow, (nt * 16 + l16) * 2, 64, 3)) =
+              pt_lds[w] + kf_swz(prow, (nt * 16 + l16) * 2, 64)) =
               kf_f32_to_bf16(p);
           *reinterpret_cast<unsigned short*>(
-              dst_lds[w] + kf_swz2(prow, (nt * 16 + l16) * 2, 64, 3)) =
+              dst_lds[w] + kf_swz(prow, (nt * 16 + l16) * 2, 64)) =
               kf_f32_to_bf16(ds);
         }
       }
@@ -320,17 +310,17 @@ __global__ __launch_bounds__(256) void kf_attn_dkv_kernel(
 
       // dV += P^T dO (B = dOt), dK += dS^T Q (B = Qt); K-dim = q (32) = 1 step
       kf_bf16x8 ptf = *reinterpret_cast<const kf_bf16x8*>(
-          pt_lds[w] + kf_swz2(l16, lg * 16, 64, 3));
+          pt_lds[w] + kf_swz(l16, lg * 16, 64));
       kf_bf16x8 dstf = *reinterpret_cast<const kf_bf16x8*>(
-          dst_lds[w] + kf_swz2(l16, lg * 16, 64, 3));
+          dst_lds[w] + kf_swz(l16, lg * 16, 64));
 #pragma unroll
       for (int nt = 0; nt < 8; ++nt) {
         kf_bf16x8 dob = *reinterpret_cast<const kf_bf16x8*>(
-            dot_lds + kf_swz2(nt * 16 + l16, lg * 16, 64, 3));
+            dot_lds + kf_swz(nt * 16 + l16, lg * 16, 64));
         dvacc[nt] =
             __builtin_amdgcn_mfma_f32_16x16x32_bf16(ptf, dob, dvacc[nt], 0, 0, 0);
         kf_bf16x8 qb = *reinterpret_cast<const kf_bf16x8*>(
-            qt_lds + kf_swz2(nt * 16 + l16, lg * 16, 64, 3));
+            qt_lds + kf_swz(nt * 16 + l16, lg * 16, 64));
         dkacc[nt] =
             __builtin_amdgcn_mfma_f32_16x16x32_bf16(dstf, qb, dkacc[nt], 0, 0, 0);
       }
@@ -350,41 +340,6 @@ __global__ __launch_bounds__(256) void kf_attn_dkv_kernel(
   }
 }
 
-// 8-wave swapped backward kernels (attention_bwd8.hip)
-extern "C" int kf_attn_bwd8_dq(void*, const void*, const void*, const void*,
-                               const void*, const float*, const float*,
-                               int64_t, int64_t, int64_t, int64_t, int64_t,
-                               int64_t, int64_t, float, int, void*);
-extern "C" int kf_attn_bwd8_dkv(void*, void*, const void*, const void*,
-                                const void*, const void*, const float*,
-                                const float*, int64_t, int64_t, int64_t,
-                                int64_t, int64_t, int64_t, int64_t, float,
-                                int, void*);
-
-extern "C" int kf_attn_bwd8_dq_rope(void*, const void*, const void*,
-                                    const void*, const void*, const float*,
-                                    const float*, int64_t, int64_t, int64_t,
-                                    int64_t, int64_t, int64_t, int64_t, float,
-                                    int, const float*, const float*, int64_t,
-                                    void*);
-extern "C" int kf_attn_bwd8_dkv_rope(void*, void*, const void*, const void*,
-                                     const void*, const void*, const float*,
-                                     const float*, int64_t, int64_t, int64_t,
-                                     int64_t, int64_t, int64_t, int64_t,
-                                     float, int, const float*, const float*,
-                                     int64_t, void*);
-extern "C" int kf_attn_bwd8_dkv_fused_rope(void*, void*, const void*,
-                                           const void*, const void*,
-                                           const void*, const float*,
-                                           const float*, int64_t, int64_t,
-                                           int64_t, int64_t, int64_t, int64_t,
-                                           int64_t, float, int, const float*,
-                                           const float*, int64_t, void*);
-
-extern "C" int kf_rope(void*, void*, const float*, const float*,
-                       const int64_t*, int64_t, int64_t, int64_t, int64_t,
-                       int64_t, int64_t, int64_t, int64_t, int, void*);
-
 // dK/dV pass on the 8-wave path: KF_ATTN_BWD_IMPL=1 selects the split
 // dv8 + dk8 pair (bisection), anything else the fused kf_attn_dkv8f kernel.
 static int kf_attn_bwd_impl() {
@@ -395,16 +350,6 @@ static int kf_attn_bwd_impl() {
   }
   return cached;
 }
-
-KF_EXPORT int kf_attn_bwd_rope(void* dq, void* dk, void* dv, const void* dout,
-                               const void* q, const void* k, const void* v,
-                               const void* o, const float* lse, float* delta,
-                               int64_t B, int64_t S, int64_t Hq, int64_t Hkv,
-                               int64_t D, int64_t qts, int64_t kts,
-                               int64_t dqts, int64_t dkts, float scale,
-                               int causal, const float* cost,
-                               const float* sint, int64_t pos_offset,
-                               void* stream);
 
 KF_EXPORT int kf_attn_bwd(void* dq, void* dk, void* dv, const void* dout,
                           const void* q, const void* k, const void* v,

@@ -17,6 +17,9 @@
 //    lgkmcnt; diagonal sub-blocks only pay the causal mask; fully-masked
 //    32-row sub-blocks are skipped per wave.
 //
+// exch() below is kf_exchange, tr() a KF_TR16 read inside kf_tr_acc_loop; the
+// lane-level derivation of both is in kf_attn_common.h.
+//
 // pass dQ (block = b, hq, 256-row q-tile; wave = 32 q rows):
 //   S^T = mfma(K, Q), dP^T = mfma(V, dO)      K/V subtiled in LDS
 //   dS^T = P^T ∘ (dP^T − delta) · scale       (registers; P via exp2)
@@ -44,61 +47,14 @@
 // (d, d+64) in one lane, so the separate kf_rope(backward=1) pass over
 // dq/dk is not needed.
 
-#include "kf_common.h"
-
-typedef __bf16 kf_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float kf_f32x16 __attribute__((ext_vector_type(16)));
-typedef short kf_short4b __attribute__((ext_vector_type(4)));
+#include "kf_attn_common.h"
 
 #define AB_D 128
-#define AB_LOG2E 1.44269504f
 
-// subtiled layout shared with the fwd kernel: element offset of X[r][d]
-// (r = the streamed row axis, 64-row tiles; d = 0..127)
-__device__ __forceinline__ int kf_vsub8(int r, int d) {
-  return ((d >> 4) << 10) + ((r >> 2) << 6) + ((r & 3) << 4) + (d & 15);
-}
-
-// row-chunk b128 read address: elements (r, d0..d0+8), d0 % 8 == 0
-__device__ __forceinline__ int kf_subrow8(int r, int byte_in_row) {
-  return 2 * kf_vsub8(r, byte_in_row >> 1);
-}
-
-__device__ __forceinline__ unsigned int kf_cvt_pk_bf16b(float lo, float hi) {
-  unsigned int r;
-  asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
-__device__ __forceinline__ float kf_exp2b(float x) {
-  float r;
-  asm volatile("v_exp_f32 %0, %1" : "=v"(r) : "v"(x));
-  return r;
-}
-
-#define KF_TR16_B(dst, addr, OFFLIT)                                    \
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:" OFFLIT               \
-               : "=v"(dst) : "v"(addr))
-
-// exchange an f32x16 acc half (8 regs from `base`) into one bf16x8 fragment
-// whose k-chunks follow the (lane>>5)*8 layout (see fwd v3 derivation).
-__device__ __forceinline__ kf_bf16x8 kf_exchange8(const kf_f32x16& a,
-                                                  int base) {
-  unsigned int w0 = kf_cvt_pk_bf16b(a[base + 0], a[base + 1]);
-  unsigned int w1 = kf_cvt_pk_bf16b(a[base + 2], a[base + 3]);
-  unsigned int w2 = kf_cvt_pk_bf16b(a[base + 4], a[base + 5]);
-  unsigned int w3 = kf_cvt_pk_bf16b(a[base + 6], a[base + 7]);
-  auto s02 = __builtin_amdgcn_permlane32_swap(w0, w2, false, false);
-  auto s13 = __builtin_amdgcn_permlane32_swap(w1, w3, false, false);
-  unsigned int u[4] = {(unsigned)s02[0], (unsigned)s13[0], (unsigned)s02[1],
-                       (unsigned)s13[1]};
-  return *reinterpret_cast<kf_bf16x8*>(u);
-}
-
-// tr_read per-lane base byte offset within one subtiled 64x128 buffer
-__device__ __forceinline__ unsigned kf_tr_lane_off(int lane) {
-  const int g = lane >> 4;
-  return (unsigned)(((g & 1) << 11) + ((g >> 1) << 8) + ((lane & 15) << 3));
+// row-chunk b128 read address in a subtiled 64-row tile (kf_vsub<64>):
+// elements (r, d0..d0+8), d0 % 8 == 0
+__device__ __forceinline__ int kf_subrow(int r, int byte_in_row) {
+  return 2 * kf_vsub<64>(r, byte_in_row >> 1);
 }
 
 // RoPE adjoint on one rotate-half pair (d, d+64) held as fp32 accumulators.
@@ -112,73 +68,6 @@ __device__ __forceinline__ unsigned kf_tr_lane_off(int lane) {
     const float t1_ = b_ * (s), t2_ = a_ * (s);                       \
     (x1) = __builtin_fmaf(a_, (c), t1_);                              \
     (x2) = __builtin_fmaf(b_, (c), -t2_);                             \
-  }
-
-// accumulate acc[dt] += mfma(tr-frag(dt), pb[step]) over dt=0..3 with a
-// 1-deep tr_read prefetch (identical loop to the fwd v4 pv_block).
-#define KF_TR_ACC_LOOP(acc, vbase, pb0, pb1)                                 \
-  {                                                                          \
-    kf_short4b t_[2][4];                                                     \
-    KF_TR16_B(t_[0][0], (vbase), "0");                                       \
-    KF_TR16_B(t_[0][1], (vbase), "128");                                     \
-    KF_TR16_B(t_[0][2], (vbase), "512");                                     \
-    KF_TR16_B(t_[0][3], (vbase), "640");                                     \
-    _Pragma("unroll") for (int dt = 0; dt < 4; ++dt) {                       \
-      if (dt < 3) {                                                          \
-        const unsigned va_ = (vbase) + ((dt + 1) << 12);                     \
-        KF_TR16_B(t_[(dt + 1) & 1][0], va_, "0");                            \
-        KF_TR16_B(t_[(dt + 1) & 1][1], va_, "128");                          \
-        KF_TR16_B(t_[(dt + 1) & 1][2], va_, "512");                          \
-        KF_TR16_B(t_[(dt + 1) & 1][3], va_, "640");                          \
-        asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");                   \
-      } else {                                                               \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                   \
-      }                                                                      \
-      __builtin_amdgcn_sched_barrier(0);                                     \
-      kf_short8 f0_ = __builtin_shufflevector(t_[dt & 1][0], t_[dt & 1][1],  \
-                                              0, 1, 2, 3, 4, 5, 6, 7);       \
-      kf_short8 f1_ = __builtin_shufflevector(t_[dt & 1][2], t_[dt & 1][3],  \
-                                              0, 1, 2, 3, 4, 5, 6, 7);       \
-      __builtin_amdgcn_s_setprio(1);                                         \
-      acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(                     \
-          *reinterpret_cast<kf_bf16x8*>(&f0_), (pb0), acc[dt], 0, 0, 0);     \
-      acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(                     \
-          *reinterpret_cast<kf_bf16x8*>(&f1_), (pb1), acc[dt], 0, 0, 0);     \
-      __builtin_amdgcn_s_setprio(0);                                         \
-    }                                                                        \
-  }
-
-// variant with the tr-frag as the B operand (dV += mfma(pa, tr(dO)))
-#define KF_TR_ACC_LOOP_B(acc, vbase, pa0, pa1)                               \
-  {                                                                          \
-    kf_short4b t_[2][4];                                                     \
-    KF_TR16_B(t_[0][0], (vbase), "0");                                       \
-    KF_TR16_B(t_[0][1], (vbase), "128");                                     \
-    KF_TR16_B(t_[0][2], (vbase), "512");                                     \
-    KF_TR16_B(t_[0][3], (vbase), "640");                                     \
-    _Pragma("unroll") for (int dt = 0; dt < 4; ++dt) {                       \
-      if (dt < 3) {                                                          \
-        const unsigned va_ = (vbase) + ((dt + 1) << 12);                     \
-        KF_TR16_B(t_[(dt + 1) & 1][0], va_, "0");                            \
-        KF_TR16_B(t_[(dt + 1) & 1][1], va_, "128");                          \
-        KF_TR16_B(t_[(dt + 1) & 1][2], va_, "512");                          \
-        KF_TR16_B(t_[(dt + 1) & 1][3], va_, "640");                          \
-        asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");                   \
-      } else {                                                               \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                   \
-      }                                                                      \
-      __builtin_amdgcn_sched_barrier(0);                                     \
-      kf_short8 f0_ = __builtin_shufflevector(t_[dt & 1][0], t_[dt & 1][1],  \
-                                              0, 1, 2, 3, 4, 5, 6, 7);       \
-      kf_short8 f1_ = __builtin_shufflevector(t_[dt & 1][2], t_[dt & 1][3],  \
-                                              0, 1, 2, 3, 4, 5, 6, 7);       \
-      __builtin_amdgcn_s_setprio(1);                                         \
-      acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(                     \
-          (pa0), *reinterpret_cast<kf_bf16x8*>(&f0_), acc[dt], 0, 0, 0);     \
-      acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(                     \
-          (pa1), *reinterpret_cast<kf_bf16x8*>(&f1_), acc[dt], 0, 0, 0);     \
-      __builtin_amdgcn_s_setprio(0);                                         \
-    }                                                                        \
   }
 
 // ---------------------------------------------------------------- pass dQ --
@@ -209,7 +98,7 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dq8_kernel(
   const int lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
   const int qrow_g = qt * DQ8_QT + w * 32 + l31;
   const int wave_qmax = qt * DQ8_QT + w * 32 + 31;
-  const float scale2 = scale * AB_LOG2E;
+  const float scale2 = scale * KF_LOG2E;
 
   // persistent B-fragments of Q and dO for this lane's q column
   kf_bf16x8 qfrag[8], dofrag[8];
@@ -225,7 +114,7 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dq8_kernel(
     }
   }
   const float lse2_q =
-      lse[(b * Hq + hq) * (int64_t)S + qrow_g] * AB_LOG2E;
+      lse[(b * Hq + hq) * (int64_t)S + qrow_g] * KF_LOG2E;
   const float dlt_q = delta[(b * Hq + hq) * (int64_t)S + qrow_g];
 
   kf_f32x16 dqacc[4];
@@ -235,7 +124,7 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dq8_kernel(
   const unsigned short* kg0 = k + (b * S) * kts + (int64_t)hkv * AB_D;
   const unsigned short* vg0 = v + (b * S) * kts + (int64_t)hkv * AB_D;
   const int sr0 = tid >> 4, sr1 = (tid + 512) >> 4, c8 = tid & 15;
-  const unsigned tr_off = kf_tr_lane_off(lane);
+  const unsigned tr_off = kf_tr_lane_off<64>(lane);
 
   const int last_kt =
       causal ? (qt * DQ8_QT + DQ8_QT - 1) / DQ8_KT : (S / DQ8_KT - 1);
@@ -246,10 +135,17 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dq8_kernel(
   kst1 = *reinterpret_cast<const kf_short8*>(kg0 + sr1 * kts + c8 * 8);
   vst0 = *reinterpret_cast<const kf_short8*>(vg0 + sr0 * kts + c8 * 8);
   vst1 = *reinterpret_cast<const kf_short8*>(vg0 + sr1 * kts + c8 * 8);
-  *reinterpret_cast<kf_short8*>(k_lds[0] + 2 * kf_vsub8(sr0, c8 * 8)) = kst0;
-  *reinterpret_cast<kf_short8*>(k_lds[0] + 2 * kf_vsub8(sr1, c8 * 8)) = kst1;
-  *reinterpret_cast<kf_short8*>(v_lds[0] + 2 * kf_vsub8(sr0, c8 * 8)) = vst0;
-  *reinterpret_cast<kf_short8*>(v_lds[0] + 2 * kf_vsub8(sr1, c8 * 8)) = vst1;
+  auto stage_write = [&](int buf) {
+    *reinterpret_cast<kf_short8*>(k_lds[buf] + 2 * kf_vsub<64>(sr0, c8 * 8)) =
+        kst0;
+    *reinterpret_cast<kf_short8*>(k_lds[buf] + 2 * kf_vsub<64>(sr1, c8 * 8)) =
+        kst1;
+    *reinterpret_cast<kf_short8*>(v_lds[buf] + 2 * kf_vsub<64>(sr0, c8 * 8)) =
+        vst0;
+    *reinterpret_cast<kf_short8*>(v_lds[buf] + 2 * kf_vsub<64>(sr1, c8 * 8)) =
+        vst1;
+  };
+  stage_write(0);
   __syncthreads();
 
   for (int kt = 0; kt <= last_kt; ++kt) {
@@ -273,11 +169,11 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dq8_kernel(
 #pragma unroll
       for (int kk = 0; kk < 8; ++kk) {
         kf_bf16x8 ka = *reinterpret_cast<const kf_bf16x8*>(
-            k_lds[cur] + kf_subrow8(mt * 32 + l31, kk * 32 + hi * 16));
+            k_lds[cur] + kf_subrow(mt * 32 + l31, kk * 32 + hi * 16));
         st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, qfrag[kk], st, 0, 0,
                                                      0);
         kf_bf16x8 va = *reinterpret_cast<const kf_bf16x8*>(
-            v_lds[cur] + kf_subrow8(mt * 32 + l31, kk * 32 + hi * 16));
+            v_lds[cur] + kf_subrow(mt * 32 + l31, kk * 32 + hi * 16));
         dpt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, dofrag[kk], dpt, 0,
                                                       0, 0);
       }
@@ -291,33 +187,23 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dq8_kernel(
           const int kv = kv0 + (r & 3) + 8 * (r >> 2);
           const float p = (kv > qrow_g)
                               ? 0.f
-                              : kf_exp2b(st[r] * scale2 - lse2_q);
+                              : kf_exp2(st[r] * scale2 - lse2_q);
           st[r] = p * (dpt[r] - dlt_q) * scale;  // dS^T
         }
       } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float p = kf_exp2b(st[r] * scale2 - lse2_q);
+          const float p = kf_exp2(st[r] * scale2 - lse2_q);
           st[r] = p * (dpt[r] - dlt_q) * scale;
         }
       }
-      kf_bf16x8 pb0 = kf_exchange8(st, 0), pb1 = kf_exchange8(st, 8);
+      kf_bf16x8 pb0 = kf_exchange(st, 0), pb1 = kf_exchange(st, 8);
       const unsigned vbase =
           (unsigned)(size_t)(k_lds[cur]) + tr_off + (mt << 10);
-      KF_TR_ACC_LOOP(dqacc, vbase, pb0, pb1);
+      kf_tr_acc_loop<true, 64>(dqacc, vbase, pb0, pb1);
     }
 
-    if (have_next) {
-      const int nxt = cur ^ 1;
-      *reinterpret_cast<kf_short8*>(k_lds[nxt] + 2 * kf_vsub8(sr0, c8 * 8)) =
-          kst0;
-      *reinterpret_cast<kf_short8*>(k_lds[nxt] + 2 * kf_vsub8(sr1, c8 * 8)) =
-          kst1;
-      *reinterpret_cast<kf_short8*>(v_lds[nxt] + 2 * kf_vsub8(sr0, c8 * 8)) =
-          vst0;
-      *reinterpret_cast<kf_short8*>(v_lds[nxt] + 2 * kf_vsub8(sr1, c8 * 8)) =
-          vst1;
-    }
+    if (have_next) stage_write(cur ^ 1);
     __syncthreads();
   }
 
@@ -351,8 +237,8 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dq8_kernel(
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         q4[j] = kf_f32_to_bf16(dqacc[dt][rq * 4 + j]);
-      *reinterpret_cast<kf_short4b*>(dq + dqb + d0) =
-          *reinterpret_cast<kf_short4b*>(q4);
+      *reinterpret_cast<kf_short4*>(dq + dqb + d0) =
+          *reinterpret_cast<kf_short4*>(q4);
     }
 }
 
@@ -387,7 +273,7 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dv8_kernel(
   const int lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
   const int kvrow_g = kt * DKV8_KT + w * 32 + l31;
   const int wave_kv_min = kt * DKV8_KT + w * 32;
-  const float scale2 = scale * AB_LOG2E;
+  const float scale2 = scale * KF_LOG2E;
 
   const unsigned short* kvb_k =
       k + (b * S + kvrow_g) * kts + (int64_t)hkv * AB_D;
@@ -409,7 +295,7 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dv8_kernel(
   const int per_head = nqt - qt0;
   const int total = g * per_head;
   const int sr0 = tid >> 4, sr1 = (tid + 512) >> 4, c8 = tid & 15;
-  const unsigned tr_off = kf_tr_lane_off(lane);
+  const unsigned tr_off = kf_tr_lane_off<64>(lane);
 
   // async-STAGE split (T14): loads issue at the top of the iteration, LDS
   // writes land after compute has covered the HBM latency.
@@ -432,14 +318,14 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dv8_kernel(
         dog + sr1 * (int64_t)Hq * AB_D + c8 * 8);
   };
   auto stage_write = [&](int buf) {
-    if (tid < DKV8_QT) lse_s[buf][tid] = lse_ld * AB_LOG2E;
-    *reinterpret_cast<kf_short8*>(q_lds[buf] + 2 * kf_vsub8(sr0, c8 * 8)) =
+    if (tid < DKV8_QT) lse_s[buf][tid] = lse_ld * KF_LOG2E;
+    *reinterpret_cast<kf_short8*>(q_lds[buf] + 2 * kf_vsub<64>(sr0, c8 * 8)) =
         sq0;
-    *reinterpret_cast<kf_short8*>(q_lds[buf] + 2 * kf_vsub8(sr1, c8 * 8)) =
+    *reinterpret_cast<kf_short8*>(q_lds[buf] + 2 * kf_vsub<64>(sr1, c8 * 8)) =
         sq1;
-    *reinterpret_cast<kf_short8*>(dot_lds[buf] + 2 * kf_vsub8(sr0, c8 * 8)) =
+    *reinterpret_cast<kf_short8*>(dot_lds[buf] + 2 * kf_vsub<64>(sr0, c8 * 8)) =
         sd0;
-    *reinterpret_cast<kf_short8*>(dot_lds[buf] + 2 * kf_vsub8(sr1, c8 * 8)) =
+    *reinterpret_cast<kf_short8*>(dot_lds[buf] + 2 * kf_vsub<64>(sr1, c8 * 8)) =
         sd1;
   };
 
@@ -462,7 +348,7 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dv8_kernel(
 #pragma unroll
       for (int kk = 0; kk < 8; ++kk) {
         kf_bf16x8 qa = *reinterpret_cast<const kf_bf16x8*>(
-            q_lds[cur] + kf_subrow8(mt * 32 + l31, kk * 32 + hi * 16));
+            q_lds[cur] + kf_subrow(mt * 32 + l31, kk * 32 + hi * 16));
         sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, kbf[kk], sacc, 0,
                                                        0, 0);
       }
@@ -477,19 +363,19 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dv8_kernel(
           const int qq = qt * DKV8_QT + ql;
           sacc[r] = (kvrow_g > qq)
                         ? 0.f
-                        : kf_exp2b(sacc[r] * scale2 - lse_s[cur][ql]);
+                        : kf_exp2(sacc[r] * scale2 - lse_s[cur][ql]);
         }
       } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int ql = q0 + (r & 3) + 8 * (r >> 2);
-          sacc[r] = kf_exp2b(sacc[r] * scale2 - lse_s[cur][ql]);
+          sacc[r] = kf_exp2(sacc[r] * scale2 - lse_s[cur][ql]);
         }
       }
-      kf_bf16x8 pa0 = kf_exchange8(sacc, 0), pa1 = kf_exchange8(sacc, 8);
+      kf_bf16x8 pa0 = kf_exchange(sacc, 0), pa1 = kf_exchange(sacc, 8);
       const unsigned vbase =
           (unsigned)(size_t)(dot_lds[cur]) + tr_off + (mt << 10);
-      KF_TR_ACC_LOOP_B(dvacc, vbase, pa0, pa1);
+      kf_tr_acc_loop<false, 64>(dvacc, vbase, pa0, pa1);
     }
     if (have_next) stage_write(cur ^ 1);
     __syncthreads();
@@ -528,7 +414,7 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dk8_kernel(
   const int lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
   const int kvrow_g = kt * DKV8_KT + w * 32 + l31;
   const int wave_kv_min = kt * DKV8_KT + w * 32;
-  const float scale2 = scale * AB_LOG2E;
+  const float scale2 = scale * KF_LOG2E;
 
   const unsigned short* kvb_k =
       k + (b * S + kvrow_g) * kts + (int64_t)hkv * AB_D;
@@ -552,7 +438,7 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dk8_kernel(
   const int per_head = nqt - qt0;
   const int total = g * per_head;
   const int sr0 = tid >> 4, sr1 = (tid + 512) >> 4, c8 = tid & 15;
-  const unsigned tr_off = kf_tr_lane_off(lane);
+  const unsigned tr_off = kf_tr_lane_off<64>(lane);
 
   kf_short8 sq0, sq1, sd0, sd1;
   float lse_ld = 0.f, dlt_ld = 0.f;
@@ -576,15 +462,15 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dk8_kernel(
         dog + sr1 * (int64_t)Hq * AB_D + c8 * 8);
   };
   auto stage_write = [&](int buf) {
-    if (tid < DKV8_QT) lse_s2[buf][tid] = lse_ld * AB_LOG2E;
+    if (tid < DKV8_QT) lse_s2[buf][tid] = lse_ld * KF_LOG2E;
     else if (tid < 2 * DKV8_QT) dlt_s2[buf][tid - DKV8_QT] = dlt_ld;
-    *reinterpret_cast<kf_short8*>(q_lds[buf] + 2 * kf_vsub8(sr0, c8 * 8)) =
+    *reinterpret_cast<kf_short8*>(q_lds[buf] + 2 * kf_vsub<64>(sr0, c8 * 8)) =
         sq0;
-    *reinterpret_cast<kf_short8*>(q_lds[buf] + 2 * kf_vsub8(sr1, c8 * 8)) =
+    *reinterpret_cast<kf_short8*>(q_lds[buf] + 2 * kf_vsub<64>(sr1, c8 * 8)) =
         sq1;
-    *reinterpret_cast<kf_short8*>(do_lds[buf] + 2 * kf_vsub8(sr0, c8 * 8)) =
+    *reinterpret_cast<kf_short8*>(do_lds[buf] + 2 * kf_vsub<64>(sr0, c8 * 8)) =
         sd0;
-    *reinterpret_cast<kf_short8*>(do_lds[buf] + 2 * kf_vsub8(sr1, c8 * 8)) =
+    *reinterpret_cast<kf_short8*>(do_lds[buf] + 2 * kf_vsub<64>(sr1, c8 * 8)) =
         sd1;
   };
 
@@ -606,11 +492,11 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dk8_kernel(
 #pragma unroll
       for (int kk = 0; kk < 8; ++kk) {
         kf_bf16x8 qa = *reinterpret_cast<const kf_bf16x8*>(
-            q_lds[cur] + kf_subrow8(mt * 32 + l31, kk * 32 + hi * 16));
+            q_lds[cur] + kf_subrow(mt * 32 + l31, kk * 32 + hi * 16));
         sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, kbf[kk], sacc, 0,
                                                        0, 0);
         kf_bf16x8 da = *reinterpret_cast<const kf_bf16x8*>(
-            do_lds[cur] + kf_subrow8(mt * 32 + l31, kk * 32 + hi * 16));
+            do_lds[cur] + kf_subrow(mt * 32 + l31, kk * 32 + hi * 16));
         dpacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, vbf[kk], dpacc,
                                                         0, 0, 0);
       }
@@ -626,21 +512,21 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dk8_kernel(
           const float p =
               (kvrow_g > qq)
                   ? 0.f
-                  : kf_exp2b(sacc[r] * scale2 - lse_s2[cur][ql]);
+                  : kf_exp2(sacc[r] * scale2 - lse_s2[cur][ql]);
           sacc[r] = p * (dpacc[r] - dlt_s2[cur][ql]) * scale;  // dS
         }
       } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int ql = q0 + (r & 3) + 8 * (r >> 2);
-          const float p = kf_exp2b(sacc[r] * scale2 - lse_s2[cur][ql]);
+          const float p = kf_exp2(sacc[r] * scale2 - lse_s2[cur][ql]);
           sacc[r] = p * (dpacc[r] - dlt_s2[cur][ql]) * scale;
         }
       }
-      kf_bf16x8 ds0 = kf_exchange8(sacc, 0), ds1 = kf_exchange8(sacc, 8);
+      kf_bf16x8 ds0 = kf_exchange(sacc, 0), ds1 = kf_exchange(sacc, 8);
       const unsigned vbase =
           (unsigned)(size_t)(q_lds[cur]) + tr_off + (mt << 10);
-      KF_TR_ACC_LOOP_B(dkacc, vbase, ds0, ds1);
+      kf_tr_acc_loop<false, 64>(dkacc, vbase, ds0, ds1);
     }
     if (have_next) stage_write(cur ^ 1);
     __syncthreads();
@@ -721,17 +607,17 @@ __global__ __launch_bounds__(DKVF_THREADS, 2) void kf_attn_dkv8f_kernel(
   const int lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
   const int kvrow_g = kt * DKVF_KT + w * 32 + l31;
   const int wave_kv_min = kt * DKVF_KT + w * 32;
-  const float scale2 = scale * AB_LOG2E;
+  const float scale2 = scale * KF_LOG2E;
 
   const unsigned short* kvb_k =
       k + (b * S + kvrow_g) * kts + (int64_t)hkv * AB_D;
   const unsigned short* kvb_v =
       v + (b * S + kvrow_g) * kts + (int64_t)hkv * AB_D;
   kf_bf16x8 kbf[8];  // persistent K B-fragments (see dv8 note)
-  // chunk kk of the lane's row lives in d-slab kk: kf_subrow8(r, kk * 32 +
-  // hi * 16) == kf_subrow8(r, hi * 16) + kk * DKVF_SLAB (64 rows x 16 d x 2 B)
+  // chunk kk of the lane's row lives in d-slab kk: kf_subrow(r, kk * 32 +
+  // hi * 16) == kf_subrow(r, hi * 16) + kk * DKVF_SLAB (64 rows x 16 d x 2 B)
   unsigned char* vfrag =
-      v_lds[w >> 1] + kf_subrow8((w & 1) * 32 + l31, hi * 16);
+      v_lds[w >> 1] + kf_subrow((w & 1) * 32 + l31, hi * 16);
 #pragma unroll
   for (int kk = 0; kk < 8; ++kk) {
     kbf[kk] =
@@ -752,7 +638,7 @@ __global__ __launch_bounds__(DKVF_THREADS, 2) void kf_attn_dkv8f_kernel(
   const int per_head = nqt - qt0;
   const int total = g * per_head;
   const int c8 = tid & 15;
-  const unsigned tr_off = kf_tr_lane_off(lane);
+  const unsigned tr_off = kf_tr_lane_off<64>(lane);
   // per-lane staging offsets kept 32-bit (uniform 64-bit base + lane offset)
   constexpr int kRowsPerPass = DKVF_THREADS / 16;
   const unsigned qoff = (unsigned)((tid >> 4) * (int)qts + c8 * 8);
@@ -781,14 +667,14 @@ __global__ __launch_bounds__(DKVF_THREADS, 2) void kf_attn_dkv8f_kernel(
     }
   };
   auto stage_write = [&](int buf) {
-    if (tid < DKV8_QT) lse_s3[buf][tid] = rc_ld * AB_LOG2E;
+    if (tid < DKV8_QT) lse_s3[buf][tid] = rc_ld * KF_LOG2E;
     else if (tid < 2 * DKV8_QT) dlt_s3[buf][tid - DKV8_QT] = rc_ld;
 #pragma unroll
     for (int j = 0; j < DKVF_NST; ++j) {
       const int sr = (tid + j * DKVF_THREADS) >> 4;
-      *reinterpret_cast<kf_short8*>(q_lds[buf] + 2 * kf_vsub8(sr, c8 * 8)) =
+      *reinterpret_cast<kf_short8*>(q_lds[buf] + 2 * kf_vsub<64>(sr, c8 * 8)) =
           sq[j];
-      *reinterpret_cast<kf_short8*>(do_lds[buf] + 2 * kf_vsub8(sr, c8 * 8)) =
+      *reinterpret_cast<kf_short8*>(do_lds[buf] + 2 * kf_vsub<64>(sr, c8 * 8)) =
           sd[j];
     }
   };
@@ -811,11 +697,11 @@ __global__ __launch_bounds__(DKVF_THREADS, 2) void kf_attn_dkv8f_kernel(
 #pragma unroll
       for (int kk = 0; kk < 8; ++kk) {
         kf_bf16x8 qa = *reinterpret_cast<const kf_bf16x8*>(
-            q_lds[cur] + kf_subrow8(mt * 32 + l31, kk * 32 + hi * 16));
+            q_lds[cur] + kf_subrow(mt * 32 + l31, kk * 32 + hi * 16));
         sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, kbf[kk], sacc, 0,
                                                        0, 0);
         kf_bf16x8 da = *reinterpret_cast<const kf_bf16x8*>(
-            do_lds[cur] + kf_subrow8(mt * 32 + l31, kk * 32 + hi * 16));
+            do_lds[cur] + kf_subrow(mt * 32 + l31, kk * 32 + hi * 16));
         kf_bf16x8 vb =
             *reinterpret_cast<const kf_bf16x8*>(vfrag + kk * DKVF_SLAB);
         dpacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, vb, dpacc, 0, 0,
@@ -833,29 +719,29 @@ __global__ __launch_bounds__(DKVF_THREADS, 2) void kf_attn_dkv8f_kernel(
           const int qq = qt * DKV8_QT + ql;
           sacc[r] = (kvrow_g > qq)
                         ? 0.f
-                        : kf_exp2b(sacc[r] * scale2 - lse_s3[cur][ql]);
+                        : kf_exp2(sacc[r] * scale2 - lse_s3[cur][ql]);
         }
       } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int ql = q0 + (r & 3) + 8 * (r >> 2);
-          sacc[r] = kf_exp2b(sacc[r] * scale2 - lse_s3[cur][ql]);
+          sacc[r] = kf_exp2(sacc[r] * scale2 - lse_s3[cur][ql]);
         }
       }
-      kf_bf16x8 pa0 = kf_exchange8(sacc, 0), pa1 = kf_exchange8(sacc, 8);
+      kf_bf16x8 pa0 = kf_exchange(sacc, 0), pa1 = kf_exchange(sacc, 8);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int ql = q0 + (r & 3) + 8 * (r >> 2);
         sacc[r] = sacc[r] * (dpacc[r] - dlt_s3[cur][ql]) * scale;  // dS
       }
-      kf_bf16x8 ds0 = kf_exchange8(sacc, 0), ds1 = kf_exchange8(sacc, 8);
+      kf_bf16x8 ds0 = kf_exchange(sacc, 0), ds1 = kf_exchange(sacc, 8);
 
       const unsigned vbase_do =
           (unsigned)(size_t)(do_lds[cur]) + tr_off + (mt << 10);
-      KF_TR_ACC_LOOP_B(dvacc, vbase_do, pa0, pa1);
+      kf_tr_acc_loop<false, 64>(dvacc, vbase_do, pa0, pa1);
       const unsigned vbase_q =
           (unsigned)(size_t)(q_lds[cur]) + tr_off + (mt << 10);
-      KF_TR_ACC_LOOP_B(dkacc, vbase_q, ds0, ds1);
+      kf_tr_acc_loop<false, 64>(dkacc, vbase_q, ds0, ds1);
     }
     if (have_next) stage_write(cur ^ 1);
     __syncthreads();

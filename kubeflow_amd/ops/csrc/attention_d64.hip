@@ -21,7 +21,8 @@
 // Math is the swapped form of kf_attn_fwd8: S^T = mfma(K, Q) puts one q row
 // in each lane's accumulator column, so the online-softmax max/sum are
 // register reductions plus one shfl_xor(32); P^T/dS^T turn into MFMA
-// B-fragments in registers (cvt_pk + permlane32_swap), never through LDS.
+// B-fragments in registers (cvt_pk + permlane32_swap: kf_exchange, derived
+// in kf_attn_common.h), never through LDS.
 // Softmax runs in the exp2 domain. C/D layout of mfma_f32_32x32x16_bf16:
 // col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
 //
@@ -48,13 +49,7 @@
 // straddle kv_len or the causal diagonal; dK/dV rows >= kv_len are stored
 // as exact zeros.
 
-#include "kf_common.h"
-
-typedef __bf16 kf_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 kf_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float kf_f32x2 __attribute__((ext_vector_type(2)));
-typedef float kf_f32x16 __attribute__((ext_vector_type(16)));
-typedef short kf_short4c __attribute__((ext_vector_type(4)));
+#include "kf_attn_common.h"
 
 #define A6_D 64
 #define A6_BT 128        // rows owned by a block (4 waves x 32)
@@ -62,34 +57,12 @@ typedef short kf_short4c __attribute__((ext_vector_type(4)));
 #define A6_THREADS 256
 #define A6_ROWB 128      // bytes per LDS row, both orientations
 #define A6_TILEB (A6_TT * A6_ROWB)
-#define A6_LOG2E 1.44269504f
-#define A6_LN2 0.69314718f
 
-__device__ __forceinline__ int kf_swz64(int row, int byte_in_row) {
-  return row * A6_ROWB + (byte_in_row ^ ((row & 7) << 4));
-}
-
-// two fp32 -> packed bf16 pair, round-to-nearest-even (v_cvt_pk_bf16_f32)
-__device__ __forceinline__ unsigned int kf_pk_bf16_64(float lo, float hi) {
-  kf_f32x2 x = {lo, hi};
-  kf_bf16x2 y = __builtin_convertvector(x, kf_bf16x2);
-  return *reinterpret_cast<unsigned int*>(&y);
-}
-
-// accumulator half (8 regs from `base`, C layout) -> one bf16x8 fragment:
-// the lane keeps its column, the 16 C rows become the k axis with chunk
-// (lane>>5)*8 (same exchange as kf_attn_fwd8 / kf_exchange8).
-__device__ __forceinline__ kf_bf16x8 kf_exchange64(const kf_f32x16& a,
-                                                   int base) {
-  unsigned int w0 = kf_pk_bf16_64(a[base + 0], a[base + 1]);
-  unsigned int w1 = kf_pk_bf16_64(a[base + 2], a[base + 3]);
-  unsigned int w2 = kf_pk_bf16_64(a[base + 4], a[base + 5]);
-  unsigned int w3 = kf_pk_bf16_64(a[base + 6], a[base + 7]);
-  auto s02 = __builtin_amdgcn_permlane32_swap(w0, w2, false, false);
-  auto s13 = __builtin_amdgcn_permlane32_swap(w1, w3, false, false);
-  unsigned int u[4] = {(unsigned)s02[0], (unsigned)s13[0], (unsigned)s02[1],
-                       (unsigned)s13[1]};
-  return *reinterpret_cast<kf_bf16x8*>(u);
+// These kernels convert with kf_cvt_pk_bf16_builtin (see kf_attn_common.h),
+// so the accumulator -> operand exchange is instantiated on it.
+__device__ __forceinline__ kf_bf16x8 kf_exchange_builtin(const kf_f32x16& a,
+                                                         int base) {
+  return kf_exchange<kf_cvt_pk_bf16_builtin>(a, base);
 }
 
 // One 64-row x 64-d tile = 512 b128 vectors, 2 per thread.
@@ -109,8 +82,8 @@ struct kf_stage64 {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int vi = tid + A6_THREADS * j;
-      *reinterpret_cast<kf_short8*>(lds + kf_swz64(vi >> 3, (vi & 7) * 16)) =
-          x[j];
+      *reinterpret_cast<kf_short8*>(
+          lds + kf_swz(vi >> 3, (vi & 7) * 16, A6_ROWB)) = x[j];
     }
   }
   // transposed [d][row]: thread (r, c8) scatters its 8 d values down one
@@ -135,7 +108,7 @@ struct kf_stage64 {
 #pragma unroll
       for (int jj = 0; jj < 8; ++jj) {  // y element jj == x element (jj+s)&7
         const int dd = s * 8 + ((jj + s) & 7);
-        *reinterpret_cast<unsigned short*>(lds + kf_swz64(dd, r * 2)) =
+        *reinterpret_cast<unsigned short*>(lds + kf_swz(dd, r * 2, A6_ROWB)) =
             (unsigned short)(y[jj >> 1] >> ((jj & 1) * 16));
       }
     }
@@ -145,7 +118,7 @@ struct kf_stage64 {
 // A-fragment of a 32-row sub-tile: rows sub*32 + (lane&31), k-chunk kk
 #define A6_AFRAG(lds, sub, kk)                                  \
   (*reinterpret_cast<const kf_bf16x8*>(                         \
-      (lds) + kf_swz64((sub) * 32 + l31, (kk) * 32 + hi * 16)))
+      (lds) + kf_swz((sub) * 32 + l31, (kk) * 32 + hi * 16, A6_ROWB)))
 
 // acc^T[d][n] (4 consecutive d per register quad) -> one bf16 row of 64
 __device__ __forceinline__ void kf_store_row64(unsigned short* dst,
@@ -156,10 +129,12 @@ __device__ __forceinline__ void kf_store_row64(unsigned short* dst,
 #pragma unroll
     for (int rq = 0; rq < 4; ++rq) {
       unsigned int u[2] = {
-          kf_pk_bf16_64(acc[dt][rq * 4 + 0] * mul, acc[dt][rq * 4 + 1] * mul),
-          kf_pk_bf16_64(acc[dt][rq * 4 + 2] * mul, acc[dt][rq * 4 + 3] * mul)};
-      *reinterpret_cast<kf_short4c*>(dst + dt * 32 + 8 * rq + 4 * hi) =
-          *reinterpret_cast<kf_short4c*>(u);
+          kf_cvt_pk_bf16_builtin(acc[dt][rq * 4 + 0] * mul,
+                                 acc[dt][rq * 4 + 1] * mul),
+          kf_cvt_pk_bf16_builtin(acc[dt][rq * 4 + 2] * mul,
+                                 acc[dt][rq * 4 + 3] * mul)};
+      *reinterpret_cast<kf_short4*>(dst + dt * 32 + 8 * rq + 4 * hi) =
+          *reinterpret_cast<kf_short4*>(u);
     }
 }
 
@@ -180,7 +155,7 @@ __global__ __launch_bounds__(A6_THREADS, 3) void kf_attn64_fwd_kernel(
   const int lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
   const int wave_qmin = qt * A6_BT + w * 32;
   const int qrow_g = wave_qmin + l31;
-  const float scale2 = scale * A6_LOG2E;
+  const float scale2 = scale * KF_LOG2E;
 
   // persistent Q B-fragments: B[k=d][n=q], this lane holds q row qrow_g
   kf_bf16x8 qfrag[4];
@@ -264,7 +239,8 @@ __global__ __launch_bounds__(A6_THREADS, 3) void kf_attn64_fwd_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) oacc[i][r] *= alpha;
 
-      const kf_bf16x8 pb[2] = {kf_exchange64(st, 0), kf_exchange64(st, 8)};
+      const kf_bf16x8 pb[2] = {kf_exchange_builtin(st, 0),
+                               kf_exchange_builtin(st, 8)};
       // O^T += V^T P^T
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -283,7 +259,7 @@ __global__ __launch_bounds__(A6_THREADS, 3) void kf_attn64_fwd_kernel(
                  1.f / l_run);
   if (hi == 0)
     lse[(b * Hq + hq) * (int64_t)S + qrow_g] =
-        m_run * A6_LN2 + __logf(l_run);
+        m_run * KF_LN2 + __logf(l_run);
 }
 
 // ------------------------------------------------------------- pass delta --
@@ -335,7 +311,7 @@ __global__ __launch_bounds__(A6_THREADS, 2) void kf_attn64_dq_kernel(
   const int lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
   const int wave_qmin = qt * A6_BT + w * 32;
   const int qrow_g = wave_qmin + l31;
-  const float scale2 = scale * A6_LOG2E;
+  const float scale2 = scale * KF_LOG2E;
 
   kf_bf16x8 qfrag[4], dofrag[4];
   {
@@ -348,7 +324,7 @@ __global__ __launch_bounds__(A6_THREADS, 2) void kf_attn64_dq_kernel(
       dofrag[kk] = *reinterpret_cast<const kf_bf16x8*>(dp + kk * 16 + hi * 8);
     }
   }
-  const float lse2_q = lse[(b * Hq + hq) * (int64_t)S + qrow_g] * A6_LOG2E;
+  const float lse2_q = lse[(b * Hq + hq) * (int64_t)S + qrow_g] * KF_LOG2E;
   const float dlt_q = delta[(b * Hq + hq) * (int64_t)S + qrow_g];
 
   kf_f32x16 dqacc[2] = {kf_f32x16{0.f}, kf_f32x16{0.f}};
@@ -407,7 +383,8 @@ __global__ __launch_bounds__(A6_THREADS, 2) void kf_attn64_dq_kernel(
           st[r] = p * (dpt[r] - dlt_q) * scale;
         }
       }
-      const kf_bf16x8 pb[2] = {kf_exchange64(st, 0), kf_exchange64(st, 8)};
+      const kf_bf16x8 pb[2] = {kf_exchange_builtin(st, 0),
+                               kf_exchange_builtin(st, 8)};
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
@@ -453,7 +430,7 @@ __global__ __launch_bounds__(A6_THREADS, 2) void kf_attn64_dkv_kernel(
   const int lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
   const int wave_kv_min = kt * A6_BT + w * 32;
   const int kvrow_g = wave_kv_min + l31;
-  const float scale2 = scale * A6_LOG2E;
+  const float scale2 = scale * KF_LOG2E;
   unsigned short* dkp = dk + ((b * S + kvrow_g) * (int64_t)Hkv + hkv) * A6_D;
   unsigned short* dvp = dv + ((b * S + kvrow_g) * (int64_t)Hkv + hkv) * A6_D;
 
@@ -503,7 +480,7 @@ __global__ __launch_bounds__(A6_THREADS, 2) void kf_attn64_dkv_kernel(
     qs.put_cols(qt_lds, tid);
     ds.put_rows(do_lds, tid);
     ds.put_cols(dot_lds, tid);
-    if (tid < A6_TT) lse_s[tid] = rc_ld * A6_LOG2E;
+    if (tid < A6_TT) lse_s[tid] = rc_ld * KF_LOG2E;
     else if (tid < 2 * A6_TT) dlt_s[tid - A6_TT] = rc_ld;
     __syncthreads();
     if (flat + 1 < total) stage_load(flat + 1);
@@ -546,15 +523,15 @@ __global__ __launch_bounds__(A6_THREADS, 2) void kf_attn64_dkv_kernel(
             sacc[r] = __builtin_amdgcn_exp2f(sacc[r] * scale2 - lse_s[ql]);
           }
         }
-        const kf_bf16x8 pb[2] = {kf_exchange64(sacc, 0),
-                                 kf_exchange64(sacc, 8)};
+        const kf_bf16x8 pb[2] = {kf_exchange_builtin(sacc, 0),
+                                 kf_exchange_builtin(sacc, 8)};
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int ql = ql0 + (r & 3) + 8 * (r >> 2);
           sacc[r] = sacc[r] * (dpacc[r] - dlt_s[ql]) * scale;  // dS
         }
-        const kf_bf16x8 db[2] = {kf_exchange64(sacc, 0),
-                                 kf_exchange64(sacc, 8)};
+        const kf_bf16x8 db[2] = {kf_exchange_builtin(sacc, 0),
+                                 kf_exchange_builtin(sacc, 8)};
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)

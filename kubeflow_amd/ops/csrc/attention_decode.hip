@@ -19,15 +19,14 @@
 // __syncthreads). Heads beyond nwaves loop in outer chunks (extra cache
 // passes — does not occur for the Llama-3 g=4 config).
 
-#include "kf_common.h"
+#include "kf_attn_common.h"
 
 #define AD_D 128
 #define AD_TILE 64
 
-// swizzle for [64 rows][256B] LDS tiles: byte ^= ((row&7)<<4) (guide §6 G4)
-__device__ __forceinline__ int kf_swzd(int row, int byte_in_row) {
-  return row * (AD_D * 2) + (byte_in_row ^ ((row & 7) << 4));
-}
+// K/V LDS tiles are [64 rows][AD_ROWB bytes], swizzled with kf_swz; nothing
+// else of the MFMA header applies to this GEMV-like kernel.
+#define AD_ROWB (AD_D * 2)
 
 // Grid (N, Hkv, SPLITS): flash-decoding sequence split. N*Hkv blocks
 // alone (16x8 = 128 at the serving bucket) fill only half the chip and
@@ -111,22 +110,24 @@ __global__ __launch_bounds__(256) void kf_attn_decode_kernel(
         for (int u = 0; u < 4; ++u) {
           const int vi = (int)threadIdx.x + u * 256;
           const int r = vi >> 4, c8 = vi & 15;
-          *reinterpret_cast<kf_short8*>(k_lds + kf_swzd(r, c8 * 16)) = kb[u];
+          *reinterpret_cast<kf_short8*>(
+              k_lds + kf_swz(r, c8 * 16, AD_ROWB)) = kb[u];
           if (!VDIRECT)
-            *reinterpret_cast<kf_short8*>(v_lds + kf_swzd(r, c8 * 16)) =
-                vb[u];
+            *reinterpret_cast<kf_short8*>(
+                v_lds + kf_swz(r, c8 * 16, AD_ROWB)) = vb[u];
         }
       } else {
         for (int vi = threadIdx.x; vi < rows * 16; vi += blockDim.x) {
           const int r = vi >> 4, c8 = vi & 15;
           kf_short8 kv8 = *reinterpret_cast<const kf_short8*>(
               kcache + cbase + (int64_t)(t0 + r) * cstride + c8 * 8);
-          *reinterpret_cast<kf_short8*>(k_lds + kf_swzd(r, c8 * 16)) = kv8;
+          *reinterpret_cast<kf_short8*>(
+              k_lds + kf_swz(r, c8 * 16, AD_ROWB)) = kv8;
           if (!VDIRECT) {
             kf_short8 vv8 = *reinterpret_cast<const kf_short8*>(
                 vcache + cbase + (int64_t)(t0 + r) * cstride + c8 * 8);
-            *reinterpret_cast<kf_short8*>(v_lds + kf_swzd(r, c8 * 16)) =
-                vv8;
+            *reinterpret_cast<kf_short8*>(
+                v_lds + kf_swz(r, c8 * 16, AD_ROWB)) = vv8;
           }
         }
       }
@@ -138,7 +139,7 @@ __global__ __launch_bounds__(256) void kf_attn_decode_kernel(
 #pragma unroll
         for (int i = 0; i < AD_D / 8; ++i) {
           kf_short8 kv8 = *reinterpret_cast<const kf_short8*>(
-              k_lds + kf_swzd(lane, i * 16));
+              k_lds + kf_swz(lane, i * 16, AD_ROWB));
 #pragma unroll
           for (int j = 0; j < 8; ++j)
             acc += qreg[i][j] * kf_bf16_to_f32((unsigned short)kv8[j]);
@@ -166,7 +167,7 @@ __global__ __launch_bounds__(256) void kf_attn_decode_kernel(
               vcache + cbase + (int64_t)(t0 + r) * cstride + dcol);
         else
           vv8 = *reinterpret_cast<const kf_short8*>(
-              v_lds + kf_swzd(r, dcol * 2));
+              v_lds + kf_swz(r, dcol * 2, AD_ROWB));
 #pragma unroll
         for (int e = 0; e < 8; ++e)
           ov[e] += pr * kf_bf16_to_f32((unsigned short)vv8[e]);

@@ -21,20 +21,13 @@
 //  * online softmax entirely in registers/cross-lane shuffles; P makes one
 //    swizzled LDS round-trip per wave to reorient acc -> A-fragment.
 
-#include "kf_common.h"
-
-typedef __bf16 kf_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float kf_f32x4 __attribute__((ext_vector_type(4)));
+#include "kf_attn_common.h"
 
 #define AT_D 128
 #define AT_QT 128     // q rows per block
 #define AT_KT 64      // kv rows per LDS tile
 #define AT_RT 2       // 16-row MFMA row-tiles per wave (32 q rows)
 #define AT_THREADS 256
-
-__device__ __forceinline__ int kf_swz(int row, int byte_in_row, int row_bytes) {
-  return row * row_bytes + (byte_in_row ^ ((row & 7) << 4));
-}
 
 __global__ __launch_bounds__(AT_THREADS, 2) void kf_attn_fwd_kernel(
     unsigned short* __restrict__ o, float* __restrict__ lse,
@@ -240,24 +233,17 @@ __global__ __launch_bounds__(AT_THREADS, 2) void kf_attn_fwd_kernel(
 //    register reductions plus a single shfl_xor(32), no LDS round-trip and
 //    no lgkmcnt drain on the softmax path.
 //  * P^T -> PV B-fragments in-register via v_cvt_pk_bf16_f32 +
-//    permlane32_swap (guide T12): 8 cvt_pk + 4 swaps per 32-kv tile.
+//    permlane32_swap (guide T12): 8 cvt_pk + 4 swaps per 32-kv tile
+//    (kf_exchange; the derivation is in kf_attn_common.h).
 //  * K row-major and V transpose-staged in XOR-swizzled LDS as in v2;
 //    PV A-fragments (V^T) are b128 reads from Vt.
 // C/D layout for mfma_f32_32x32x16_bf16: col = lane&31,
 // row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)  [guide §3, m74/m101].
 // ---------------------------------------------------------------------------
 
-typedef float kf_f32x16 __attribute__((ext_vector_type(16)));
-
 #define A8_QT 256  // q rows per block (4-wave/128-row blocks measured 193 TF)
 #define A8_KT 128  // kv rows per LDS tile (64 -> 236 TF, 128 -> 296, 256 -> 240)
 #define A8_THREADS 512
-
-__device__ __forceinline__ unsigned int kf_cvt_pk_bf16(float lo, float hi) {
-  unsigned int r;
-  asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
 
 __global__ __launch_bounds__(A8_THREADS, 2) void kf_attn_fwd8_kernel(
     unsigned short* __restrict__ o, float* __restrict__ lse,
@@ -368,9 +354,8 @@ __global__ __launch_bounds__(A8_THREADS, 2) void kf_attn_fwd8_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) oacc[i][r] *= alpha;
 
-      // ---- P^T -> two B-fragments via cvt_pk + permlane32_swap ----
-      // regs 0-7 cover kv-local {0..3, 8..11} (+4 for hi lanes);
-      // regs 8-15 cover {16..19, 24..27} (+4 for hi lanes).
+      // ---- P^T -> two B-fragments: kf_exchange(st, 0 / 8), spelled out
+      // (calling the helper changes this kernel's register allocation) ----
       kf_bf16x8 pb[2];
 #pragma unroll
       for (int step = 0; step < 2; ++step) {
@@ -420,17 +405,9 @@ __global__ __launch_bounds__(A8_THREADS, 2) void kf_attn_fwd8_kernel(
 
 
 // Newer kernels: v4 (attention_fwd4.hip, 8-wave async-STAGE + tr_read V)
-// and v5 (attention_fwd5.hip, 4-wave x 64-q LDS-traffic-halved). Dispatch
-// order: KF_ATTN_IMPL=5 (default) -> 4 -> 3 for bisection.
-KF_EXPORT int kf_attn_fwd4(void* o, float* lse, const void* q, const void* k,
-                           const void* v, int64_t B, int64_t S, int64_t Hq,
-                           int64_t Hkv, int64_t D, int64_t qts, int64_t kts,
-                           float scale, int causal, void* stream);
-KF_EXPORT int kf_attn_fwd5(void* o, float* lse, const void* q, const void* k,
-                           const void* v, int64_t B, int64_t S, int64_t Hq,
-                           int64_t Hkv, int64_t D, int64_t qts, int64_t kts,
-                           float scale, int causal, void* stream);
-
+// and v5 (attention_fwd5.hip, 4-wave x 64-q LDS-traffic-halved, a measured
+// negative result). KF_ATTN_IMPL selects: 4 (default), 5, or 3 = the 8-wave
+// kernel above, for bisection.
 static int kf_attn_impl() {
   static int cached = -1;
   if (cached < 0) {

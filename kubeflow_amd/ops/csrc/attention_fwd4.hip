@@ -29,11 +29,7 @@
 // fp32. D == 128, S % 256 == 0 (wrapper pads). Reference behavior anchor:
 // SURVEY.md §2.13 attention_fwd row.
 
-#include "kf_common.h"
-
-typedef __bf16 kf_bf16x8v4 __attribute__((ext_vector_type(8)));
-typedef float kf_f32x16v4 __attribute__((ext_vector_type(16)));
-typedef short kf_short4v4 __attribute__((ext_vector_type(4)));
+#include "kf_attn_common.h"
 
 #define A4_D 128
 #define A4_QT 256      // q rows per block (8 waves x 32)
@@ -44,40 +40,10 @@ typedef short kf_short4v4 __attribute__((ext_vector_type(4)));
 #ifndef A4_KT
 #define A4_KT 64
 #endif
-#define A4_SLAB (A4_KT / 4 * 64)   // elems per d16-slab in the V layout
 #define A4_THREADS 512
-#define A4_LOG2E 1.44269504f
-#define A4_LN2 0.69314718f
-#define A4_RESCALE_THR2 11.5415603f  // 8 * log2(e): defer-max in exp2 units
 
-// row-major K tile swizzle (guide G4): byte ^= (row&7)<<4
-__device__ __forceinline__ int kf_swz4(int row, int byte_in_row) {
-  return row * (A4_D * 2) + (byte_in_row ^ ((row & 7) << 4));
-}
-
-// V subtile layout for ds_read_b64_tr_b16 (T10): element offset of V[kv][d]
-// = slab(d>>4)*1024 + (kv>>2)*64 + (kv&3)*16 + (d&15). Each [4][16] subtile
-// is 128 contiguous bytes; a 16-lane group's tr_read covers one subtile and
-// delivers column (lane&15): lane l receives V^T[d=base_d+(l&15)][kv=base+j].
-__device__ __forceinline__ int kf_vsub4(int kv, int d) {
-  return (d >> 4) * A4_SLAB + ((kv >> 2) << 6) + ((kv & 3) << 4) + (d & 15);
-}
-
-__device__ __forceinline__ unsigned int kf_cvt_pk_bf16_v4(float lo, float hi) {
-  unsigned int r;
-  asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
-__device__ __forceinline__ float kf_exp2(float x) {
-  float r;
-  asm volatile("v_exp_f32 %0, %1" : "=v"(r) : "v"(x));
-  return r;
-}
-
-#define KF_TR16(dst, addr, OFFLIT)                                      \
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:" OFFLIT               \
-               : "=v"(dst) : "v"(addr))
+// K tile: row-major, kf_swz. V tile: kf_vsub<A4_KT> subtiles, read as V^T
+// through KF_TR16 (layouts and lane mapping in kf_attn_common.h).
 
 // ABL ablation bits (guide m164 methodology — ablate before optimizing):
 // 1 = skip softmax math (pb straight from scaled st), 2 = skip PV MFMA
@@ -108,22 +74,22 @@ __global__ __launch_bounds__(A4_THREADS, 2) void kf_attn_fwd4_kernel(
   const int lane = tid & (KF_WAVE - 1);
   const int l31 = lane & 31;
   const int hi = lane >> 5;
-  const float scale2 = scale * A4_LOG2E;  // QK^T scaled into exp2 domain
+  const float scale2 = scale * KF_LOG2E;  // QK^T scaled into exp2 domain
 
   // ---- persistent Q B-fragments: lane holds q-col l31 ----
-  kf_bf16x8v4 qfrag[8];
+  kf_bf16x8 qfrag[8];
   {
     const int64_t qbase =
         (b * S + qt * A4_QT + w * 32 + l31) * qts + (int64_t)hq * A4_D;
 #pragma unroll
     for (int kk = 0; kk < 8; ++kk)
       qfrag[kk] =
-          *reinterpret_cast<const kf_bf16x8v4*>(q + qbase + kk * 16 + hi * 8);
+          *reinterpret_cast<const kf_bf16x8*>(q + qbase + kk * 16 + hi * 8);
   }
 
-  kf_f32x16v4 oacc[4];
+  kf_f32x16 oacc[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) oacc[i] = kf_f32x16v4{0.f};
+  for (int i = 0; i < 4; ++i) oacc[i] = kf_f32x16{0.f};
   float m_run = -INFINITY, l_run = 0.f;  // m_run in exp2 units
   const int qrow_g = qt * A4_QT + w * 32 + l31;
   const int wave_qmin = qt * A4_QT + w * 32;
@@ -147,24 +113,19 @@ __global__ __launch_bounds__(A4_THREADS, 2) void kf_attn_fwd4_kernel(
   for (int j = 0; j < A4_KT / 32; ++j)
     srow[j] = (tid + A4_THREADS * j) >> 4;
 
-  // per-lane tr_read base byte address inside a V buffer: group g covers
-  // slab (g&1), kv-subtile 2*(g>>1), column lane&15 (see kf_vsub4).
-  const int g = lane >> 4;
-  const unsigned v_lane_off =
-      (unsigned)(((g & 1) * A4_SLAB * 2) + ((g >> 1) << 8) +
-                 ((lane & 15) << 3));
+  const unsigned v_lane_off = kf_tr_lane_off<A4_KT>(lane);
 
   // ---- S^T = mfma(K, Q) over one 32-kv sub-block. All 8 K-fragment
   // ds_reads issue back-to-back BEFORE the MFMA chain so the ~120-cycle
   // LDS latency pipelines instead of serializing per MFMA (the same
   // issue-all-then-compute discipline as the guide's GEMM ladder). ----
   auto qk_block = [&](int cur, int mt) {
-    kf_bf16x8v4 af[8];
+    kf_bf16x8 af[8];
 #pragma unroll
     for (int kk = 0; kk < 8; ++kk)
-      af[kk] = *reinterpret_cast<const kf_bf16x8v4*>(
-          k_lds[cur] + kf_swz4(mt * 32 + l31, kk * 32 + hi * 16));
-    kf_f32x16v4 st = kf_f32x16v4{0.f};
+      af[kk] = *reinterpret_cast<const kf_bf16x8*>(
+          k_lds[cur] + kf_swz(mt * 32 + l31, kk * 32 + hi * 16, A4_D * 2));
+    kf_f32x16 st = kf_f32x16{0.f};
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int kk = 0; kk < 8; ++kk)
@@ -175,25 +136,14 @@ __global__ __launch_bounds__(A4_THREADS, 2) void kf_attn_fwd4_kernel(
   };
 
   // ---- defer-max online softmax (exp2 domain) + P repack (T12/T13) ----
-  auto sm_block = [&](kf_f32x16v4& st, int kv_lo, bool need_mask,
-                      kf_bf16x8v4* pb) {
+  auto sm_block = [&](kf_f32x16& st, int kv_lo, bool need_mask,
+                      kf_bf16x8* pb) {
     if (ABL & 1) {  // NOSM: scale-only, straight to repack (keeps st live)
 #pragma unroll
       for (int r = 0; r < 16; ++r) st[r] *= scale2;
       l_run += st[0];
-#pragma unroll
-      for (int step = 0; step < 2; ++step) {
-        const int base = step * 8;
-        unsigned int w0 = kf_cvt_pk_bf16_v4(st[base + 0], st[base + 1]);
-        unsigned int w1 = kf_cvt_pk_bf16_v4(st[base + 2], st[base + 3]);
-        unsigned int w2 = kf_cvt_pk_bf16_v4(st[base + 4], st[base + 5]);
-        unsigned int w3 = kf_cvt_pk_bf16_v4(st[base + 6], st[base + 7]);
-        auto s02 = __builtin_amdgcn_permlane32_swap(w0, w2, false, false);
-        auto s13 = __builtin_amdgcn_permlane32_swap(w1, w3, false, false);
-        unsigned int u[4] = {(unsigned)s02[0], (unsigned)s13[0],
-                             (unsigned)s02[1], (unsigned)s13[1]};
-        pb[step] = *reinterpret_cast<kf_bf16x8v4*>(u);
-      }
+      pb[0] = kf_exchange(st, 0);
+      pb[1] = kf_exchange(st, 8);
       return;
     }
     const int kv0 = kv_lo + hi * 4;
@@ -216,7 +166,7 @@ __global__ __launch_bounds__(A4_THREADS, 2) void kf_attn_fwd4_kernel(
       }
     }
     mx = fmaxf(mx, __shfl_xor(mx, 32, KF_WAVE));
-    if (!__all(mx <= m_run + A4_RESCALE_THR2)) {
+    if (!__all(mx <= m_run + KF_DEFER_MAX_THR2)) {
       const float m_new = fmaxf(m_run, mx);
       const float alpha = kf_exp2(m_run - m_new);  // 0 on first block
 #pragma unroll
@@ -235,61 +185,24 @@ __global__ __launch_bounds__(A4_THREADS, 2) void kf_attn_fwd4_kernel(
     }
     lsum += __shfl_xor(lsum, 32, KF_WAVE);
     l_run += lsum;
-#pragma unroll
-    for (int step = 0; step < 2; ++step) {
-      const int base = step * 8;
-      unsigned int w0 = kf_cvt_pk_bf16_v4(st[base + 0], st[base + 1]);
-      unsigned int w1 = kf_cvt_pk_bf16_v4(st[base + 2], st[base + 3]);
-      unsigned int w2 = kf_cvt_pk_bf16_v4(st[base + 4], st[base + 5]);
-      unsigned int w3 = kf_cvt_pk_bf16_v4(st[base + 6], st[base + 7]);
-      auto s02 = __builtin_amdgcn_permlane32_swap(w0, w2, false, false);
-      auto s13 = __builtin_amdgcn_permlane32_swap(w1, w3, false, false);
-      unsigned int u[4] = {(unsigned)s02[0], (unsigned)s13[0],
-                           (unsigned)s02[1], (unsigned)s13[1]};
-      pb[step] = *reinterpret_cast<kf_bf16x8v4*>(u);
-    }
+    pb[0] = kf_exchange(st, 0);
+    pb[1] = kf_exchange(st, 8);
   };
 
   // ---- O^T += V^T P^T with 1-deep tr_read prefetch ----
-  auto pv_block = [&](const kf_bf16x8v4* pb, unsigned vbase) {
+  auto pv_block = [&](const kf_bf16x8* pb, unsigned vbase) {
     if (ABL & 2) {  // NOPV: keep pb live, skip tr_reads + MFMAs
       asm volatile("" ::"v"(*(const unsigned*)&pb[0]),
                    "v"(*(const unsigned*)&pb[1]), "v"(vbase));
       oacc[0][0] += (float)pb[0][0];
       return;
     }
-    kf_short4v4 t[2][4];
-    KF_TR16(t[0][0], vbase, "0");
-    KF_TR16(t[0][1], vbase, "128");
-    KF_TR16(t[0][2], vbase, "512");
-    KF_TR16(t[0][3], vbase, "640");
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      if (dt < 3) {
-        const unsigned va = vbase + (unsigned)((dt + 1) * A4_SLAB * 4);
-        KF_TR16(t[(dt + 1) & 1][0], va, "0");
-        KF_TR16(t[(dt + 1) & 1][1], va, "128");
-        KF_TR16(t[(dt + 1) & 1][2], va, "512");
-        KF_TR16(t[(dt + 1) & 1][3], va, "640");
-        asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-      } else {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      }
-      __builtin_amdgcn_sched_barrier(0);  // guide rule 18
-      kf_short8 f0 = __builtin_shufflevector(t[dt & 1][0], t[dt & 1][1],
-                                             0, 1, 2, 3, 4, 5, 6, 7);
-      kf_short8 f1 = __builtin_shufflevector(t[dt & 1][2], t[dt & 1][3],
-                                             0, 1, 2, 3, 4, 5, 6, 7);
-      __builtin_amdgcn_s_setprio(1);
-      oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-          *reinterpret_cast<kf_bf16x8v4*>(&f0), pb[0], oacc[dt], 0, 0, 0);
-      oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-          *reinterpret_cast<kf_bf16x8v4*>(&f1), pb[1], oacc[dt], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-    }
+    kf_tr_acc_loop<true, A4_KT>(oacc, vbase, pb[0], pb[1]);
   };
 
   // ---- prologue: stage tile 0 into buffer 0 ----
+  // (the staged-tile LDS write below is spelled out three times on purpose:
+  // behind a lambda or helper the compiler allocates registers differently)
   kf_short8 kst[A4_KT / 32], vst[A4_KT / 32];
 #pragma unroll
   for (int j = 0; j < A4_KT / 32; ++j) {
@@ -298,10 +211,10 @@ __global__ __launch_bounds__(A4_THREADS, 2) void kf_attn_fwd4_kernel(
   }
 #pragma unroll
   for (int j = 0; j < A4_KT / 32; ++j) {
-    *reinterpret_cast<kf_short8*>(k_lds[0] + kf_swz4(srow[j], c8 * 16)) =
-        kst[j];
-    *reinterpret_cast<kf_short8*>(v_lds[0] + 2 * kf_vsub4(srow[j], c8 * 8)) =
-        vst[j];
+    *reinterpret_cast<kf_short8*>(
+        k_lds[0] + kf_swz(srow[j], c8 * 16, A4_D * 2)) = kst[j];
+    *reinterpret_cast<kf_short8*>(
+        v_lds[0] + 2 * kf_vsub<A4_KT>(srow[j], c8 * 8)) = vst[j];
   }
   __syncthreads();
 
@@ -334,10 +247,10 @@ __global__ __launch_bounds__(A4_THREADS, 2) void kf_attn_fwd4_kernel(
       const bool do1 = (!causal || kv_lo1 <= wave_qmax + qoff) &&
                        kv_lo1 < skv;
       if (!do0 && !do1) continue;
-      kf_f32x16v4 st0, st1;
+      kf_f32x16 st0, st1;
       if (do0) st0 = qk_block(cur, pair * 2);
       if (do1) st1 = qk_block(cur, pair * 2 + 1);
-      kf_bf16x8v4 pb[2];
+      kf_bf16x8 pb[2];
       if (do0) {
         sm_block(st0, kv_lo0,
                  (causal && kv_lo0 + 31 > wave_qmin + qoff) ||
@@ -352,11 +265,10 @@ __global__ __launch_bounds__(A4_THREADS, 2) void kf_attn_fwd4_kernel(
         const int nxt = cur ^ 1;
 #pragma unroll
         for (int j = 0; j < A4_KT / 32; ++j) {
-          *reinterpret_cast<kf_short8*>(k_lds[nxt] +
-                                        kf_swz4(srow[j], c8 * 16)) = kst[j];
-          *reinterpret_cast<kf_short8*>(v_lds[nxt] +
-                                        2 * kf_vsub4(srow[j], c8 * 8)) =
-              vst[j];
+          *reinterpret_cast<kf_short8*>(
+              k_lds[nxt] + kf_swz(srow[j], c8 * 16, A4_D * 2)) = kst[j];
+          *reinterpret_cast<kf_short8*>(
+              v_lds[nxt] + 2 * kf_vsub<A4_KT>(srow[j], c8 * 8)) = vst[j];
         }
       }
       if (do1) {
@@ -372,10 +284,10 @@ __global__ __launch_bounds__(A4_THREADS, 2) void kf_attn_fwd4_kernel(
       const int nxt = cur ^ 1;
 #pragma unroll
       for (int j = 0; j < A4_KT / 32; ++j) {
-        *reinterpret_cast<kf_short8*>(k_lds[nxt] + kf_swz4(srow[j], c8 * 16)) =
-            kst[j];
-        *reinterpret_cast<kf_short8*>(v_lds[nxt] +
-                                      2 * kf_vsub4(srow[j], c8 * 8)) = vst[j];
+        *reinterpret_cast<kf_short8*>(
+            k_lds[nxt] + kf_swz(srow[j], c8 * 16, A4_D * 2)) = kst[j];
+        *reinterpret_cast<kf_short8*>(
+            v_lds[nxt] + 2 * kf_vsub<A4_KT>(srow[j], c8 * 8)) = vst[j];
       }
     }
     __syncthreads();  // readers of [cur] done + writes to [nxt] visible
@@ -393,12 +305,12 @@ __global__ __launch_bounds__(A4_THREADS, 2) void kf_attn_fwd4_kernel(
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         q4[j] = kf_f32_to_bf16(oacc[dt][rq * 4 + j] * inv_l);
-      *reinterpret_cast<kf_short4v4*>(o + obase + d0) =
-          *reinterpret_cast<kf_short4v4*>(q4);
+      *reinterpret_cast<kf_short4*>(o + obase + d0) =
+          *reinterpret_cast<kf_short4*>(q4);
     }
   if (hi == 0)
     lse[(b * Hq + hq) * (int64_t)S + qrow_g] =
-        m_run * A4_LN2 + __logf(l_run);
+        m_run * KF_LN2 + __logf(l_run);
 }
 
 template <int ABL>
@@ -489,7 +401,7 @@ __global__ void kf_tr16_probe_kernel(short* out, const short* in, int mode) {
   if (mode == 0) addr = base + 8u * lane;          // 4 tiles, one per group
   else if (mode == 1) addr = base;                 // uniform
   else addr = base + 8u * (lane & 15);             // same tile all groups
-  kf_short4v4 r0, r1;
+  kf_short4 r0, r1;
   KF_TR16(r0, addr, "0");
   KF_TR16(r1, addr, "128");
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

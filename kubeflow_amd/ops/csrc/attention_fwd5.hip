@@ -30,43 +30,12 @@
 // Layout: bshd q [B,S,Hq,D], k/v [B,S,Hkv,D], o [B,S,Hq,D], lse [B,Hq,S]
 // fp32. D == 128, S % 256 == 0. SURVEY.md §2.13 attention_fwd row.
 
-#include "kf_common.h"
-
-typedef __bf16 kf_bf16x8v5 __attribute__((ext_vector_type(8)));
-typedef float kf_f32x16v5 __attribute__((ext_vector_type(16)));
-typedef short kf_short4v5 __attribute__((ext_vector_type(4)));
+#include "kf_attn_common.h"
 
 #define A5_D 128
 #define A5_QT 256      // q rows per block (4 waves x 64)
 #define A5_KT 64       // kv rows per LDS tile (double-buffered)
 #define A5_THREADS 256
-#define A5_LOG2E 1.44269504f
-#define A5_LN2 0.69314718f
-#define A5_THR2 11.5415603f  // 8 * log2(e): defer-max threshold, exp2 units
-
-__device__ __forceinline__ int kf_swz5(int row, int byte_in_row) {
-  return row * (A5_D * 2) + (byte_in_row ^ ((row & 7) << 4));
-}
-
-__device__ __forceinline__ int kf_vsub5(int kv, int d) {
-  return ((d >> 4) << 10) + ((kv >> 2) << 6) + ((kv & 3) << 4) + (d & 15);
-}
-
-__device__ __forceinline__ unsigned int kf_cvt_pk_bf16_v5(float lo, float hi) {
-  unsigned int r;
-  asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
-__device__ __forceinline__ float kf_exp2_v5(float x) {
-  float r;
-  asm volatile("v_exp_f32 %0, %1" : "=v"(r) : "v"(x));
-  return r;
-}
-
-#define KF_TR16_V5(dst, addr, OFFLIT)                                   \
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:" OFFLIT               \
-               : "=v"(dst) : "v"(addr))
 
 __global__ __launch_bounds__(A5_THREADS, 1) void kf_attn_fwd5_kernel(
     unsigned short* __restrict__ o, float* __restrict__ lse,
@@ -84,10 +53,10 @@ __global__ __launch_bounds__(A5_THREADS, 1) void kf_attn_fwd5_kernel(
   const int lane = tid & (KF_WAVE - 1);
   const int l31 = lane & 31;
   const int hi = lane >> 5;
-  const float scale2 = scale * A5_LOG2E;
+  const float scale2 = scale * KF_LOG2E;
 
   // ---- persistent Q B-fragments for both 32-q halves ----
-  kf_bf16x8v5 qfrag[2][8];
+  kf_bf16x8 qfrag[2][8];
 #pragma unroll
   for (int qh = 0; qh < 2; ++qh) {
     const int64_t qbase =
@@ -96,14 +65,14 @@ __global__ __launch_bounds__(A5_THREADS, 1) void kf_attn_fwd5_kernel(
 #pragma unroll
     for (int kk = 0; kk < 8; ++kk)
       qfrag[qh][kk] =
-          *reinterpret_cast<const kf_bf16x8v5*>(q + qbase + kk * 16 + hi * 8);
+          *reinterpret_cast<const kf_bf16x8*>(q + qbase + kk * 16 + hi * 8);
   }
 
-  kf_f32x16v5 oacc[4][2];  // [dt][qh]
+  kf_f32x16 oacc[4][2];  // [dt][qh]
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int qh = 0; qh < 2; ++qh) oacc[i][qh] = kf_f32x16v5{0.f};
+    for (int qh = 0; qh < 2; ++qh) oacc[i][qh] = kf_f32x16{0.f};
   float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};
   const int qrow0 = qt * A5_QT + w * 64;         // wave's first q row
   const int qrow_g0 = qrow0 + l31;               // lane's q row, half 0
@@ -120,6 +89,7 @@ __global__ __launch_bounds__(A5_THREADS, 1) void kf_attn_fwd5_kernel(
 #pragma unroll
   for (int j = 0; j < 4; ++j) srow[j] = (tid + A5_THREADS * j) >> 4;
 
+  // kf_tr_lane_off<A5_KT>(lane), spelled out: the call compiles to other code
   const int g = lane >> 4;
   const unsigned v_lane_off =
       (unsigned)(((g & 1) << 11) + ((g >> 1) << 8) + ((lane & 15) << 3));
@@ -133,10 +103,10 @@ __global__ __launch_bounds__(A5_THREADS, 1) void kf_attn_fwd5_kernel(
   }
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    *reinterpret_cast<kf_short8*>(k_lds[0] + kf_swz5(srow[j], c8 * 16)) =
-        kst[j];
-    *reinterpret_cast<kf_short8*>(v_lds[0] + 2 * kf_vsub5(srow[j], c8 * 8)) =
-        vst[j];
+    *reinterpret_cast<kf_short8*>(
+        k_lds[0] + kf_swz(srow[j], c8 * 16, A5_D * 2)) = kst[j];
+    *reinterpret_cast<kf_short8*>(
+        v_lds[0] + 2 * kf_vsub<A5_KT>(srow[j], c8 * 8)) = vst[j];
   }
   __syncthreads();
 
@@ -164,12 +134,12 @@ __global__ __launch_bounds__(A5_THREADS, 1) void kf_attn_fwd5_kernel(
       if (!act0 && !act1) continue;
 
       // ---- QK^T: one K-fragment read feeds both q-halves' chains ----
-      kf_bf16x8v5 af[8];
+      kf_bf16x8 af[8];
 #pragma unroll
       for (int kk = 0; kk < 8; ++kk)
-        af[kk] = *reinterpret_cast<const kf_bf16x8v5*>(
-            k_lds[cur] + kf_swz5(mt * 32 + l31, kk * 32 + hi * 16));
-      kf_f32x16v5 st0 = kf_f32x16v5{0.f}, st1 = kf_f32x16v5{0.f};
+        af[kk] = *reinterpret_cast<const kf_bf16x8*>(
+            k_lds[cur] + kf_swz(mt * 32 + l31, kk * 32 + hi * 16, A5_D * 2));
+      kf_f32x16 st0 = kf_f32x16{0.f}, st1 = kf_f32x16{0.f};
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int kk = 0; kk < 8; ++kk) {
@@ -183,12 +153,12 @@ __global__ __launch_bounds__(A5_THREADS, 1) void kf_attn_fwd5_kernel(
       __builtin_amdgcn_s_setprio(0);
 
       // ---- softmax per half (exp2 domain, defer-max) -> pb repack ----
-      kf_bf16x8v5 pb[2][2];  // [qh][step]
+      kf_bf16x8 pb[2][2];  // [qh][step]
       const int kv0 = kv_lo + hi * 4;
 #pragma unroll
       for (int qh = 0; qh < 2; ++qh) {
         if (!(qh ? act1 : act0)) continue;
-        kf_f32x16v5& st = qh ? st1 : st0;
+        kf_f32x16& st = qh ? st1 : st0;
         const int qrow_g = qh ? qrow_g1 : qrow_g0;
         const bool need_mask =
             causal && kv_lo + 31 > qrow0 + qh * 32;  // diagonal only
@@ -211,9 +181,9 @@ __global__ __launch_bounds__(A5_THREADS, 1) void kf_attn_fwd5_kernel(
           }
         }
         mx = fmaxf(mx, __shfl_xor(mx, 32, KF_WAVE));
-        if (!__all(mx <= m_run[qh] + A5_THR2)) {
+        if (!__all(mx <= m_run[qh] + KF_DEFER_MAX_THR2)) {
           const float m_new = fmaxf(m_run[qh], mx);
-          const float alpha = kf_exp2_v5(m_run[qh] - m_new);
+          const float alpha = kf_exp2(m_run[qh] - m_new);
 #pragma unroll
           for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -224,43 +194,32 @@ __global__ __launch_bounds__(A5_THREADS, 1) void kf_attn_fwd5_kernel(
         float lsum = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float pv = kf_exp2_v5(st[r] - m_run[qh]);
+          const float pv = kf_exp2(st[r] - m_run[qh]);
           st[r] = pv;
           lsum += pv;
         }
         lsum += __shfl_xor(lsum, 32, KF_WAVE);
         l_run[qh] += lsum;
-#pragma unroll
-        for (int step = 0; step < 2; ++step) {
-          const int base = step * 8;
-          unsigned int w0 = kf_cvt_pk_bf16_v5(st[base + 0], st[base + 1]);
-          unsigned int w1 = kf_cvt_pk_bf16_v5(st[base + 2], st[base + 3]);
-          unsigned int w2 = kf_cvt_pk_bf16_v5(st[base + 4], st[base + 5]);
-          unsigned int w3 = kf_cvt_pk_bf16_v5(st[base + 6], st[base + 7]);
-          auto s02 = __builtin_amdgcn_permlane32_swap(w0, w2, false, false);
-          auto s13 = __builtin_amdgcn_permlane32_swap(w1, w3, false, false);
-          unsigned int u[4] = {(unsigned)s02[0], (unsigned)s13[0],
-                               (unsigned)s02[1], (unsigned)s13[1]};
-          pb[qh][step] = *reinterpret_cast<kf_bf16x8v5*>(u);
-        }
+        pb[qh][0] = kf_exchange(st, 0);
+        pb[qh][1] = kf_exchange(st, 8);
       }
 
       // ---- PV: each V^T fragment pair feeds up to 4 MFMAs (2 halves) ----
       const unsigned vbase =
           (unsigned)(size_t)(v_lds[cur]) + v_lane_off + (mt << 10);
-      kf_short4v5 t[2][4];
-      KF_TR16_V5(t[0][0], vbase, "0");
-      KF_TR16_V5(t[0][1], vbase, "128");
-      KF_TR16_V5(t[0][2], vbase, "512");
-      KF_TR16_V5(t[0][3], vbase, "640");
+      kf_short4 t[2][4];
+      KF_TR16(t[0][0], vbase, "0");
+      KF_TR16(t[0][1], vbase, "128");
+      KF_TR16(t[0][2], vbase, "512");
+      KF_TR16(t[0][3], vbase, "640");
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
         if (dt < 3) {
           const unsigned va = vbase + ((dt + 1) << 12);
-          KF_TR16_V5(t[(dt + 1) & 1][0], va, "0");
-          KF_TR16_V5(t[(dt + 1) & 1][1], va, "128");
-          KF_TR16_V5(t[(dt + 1) & 1][2], va, "512");
-          KF_TR16_V5(t[(dt + 1) & 1][3], va, "640");
+          KF_TR16(t[(dt + 1) & 1][0], va, "0");
+          KF_TR16(t[(dt + 1) & 1][1], va, "128");
+          KF_TR16(t[(dt + 1) & 1][2], va, "512");
+          KF_TR16(t[(dt + 1) & 1][3], va, "640");
           asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
         } else {
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -273,18 +232,18 @@ __global__ __launch_bounds__(A5_THREADS, 1) void kf_attn_fwd5_kernel(
         __builtin_amdgcn_s_setprio(1);
         if (act0) {
           oacc[dt][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              *reinterpret_cast<kf_bf16x8v5*>(&f0), pb[0][0], oacc[dt][0],
+              *reinterpret_cast<kf_bf16x8*>(&f0), pb[0][0], oacc[dt][0],
               0, 0, 0);
           oacc[dt][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              *reinterpret_cast<kf_bf16x8v5*>(&f1), pb[0][1], oacc[dt][0],
+              *reinterpret_cast<kf_bf16x8*>(&f1), pb[0][1], oacc[dt][0],
               0, 0, 0);
         }
         if (act1) {
           oacc[dt][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              *reinterpret_cast<kf_bf16x8v5*>(&f0), pb[1][0], oacc[dt][1],
+              *reinterpret_cast<kf_bf16x8*>(&f0), pb[1][0], oacc[dt][1],
               0, 0, 0);
           oacc[dt][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              *reinterpret_cast<kf_bf16x8v5*>(&f1), pb[1][1], oacc[dt][1],
+              *reinterpret_cast<kf_bf16x8*>(&f1), pb[1][1], oacc[dt][1],
               0, 0, 0);
         }
         __builtin_amdgcn_s_setprio(0);
@@ -295,10 +254,10 @@ __global__ __launch_bounds__(A5_THREADS, 1) void kf_attn_fwd5_kernel(
       const int nxt = cur ^ 1;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        *reinterpret_cast<kf_short8*>(k_lds[nxt] + kf_swz5(srow[j], c8 * 16)) =
-            kst[j];
-        *reinterpret_cast<kf_short8*>(v_lds[nxt] +
-                                      2 * kf_vsub5(srow[j], c8 * 8)) = vst[j];
+        *reinterpret_cast<kf_short8*>(
+            k_lds[nxt] + kf_swz(srow[j], c8 * 16, A5_D * 2)) = kst[j];
+        *reinterpret_cast<kf_short8*>(
+            v_lds[nxt] + 2 * kf_vsub<A5_KT>(srow[j], c8 * 8)) = vst[j];
       }
     }
     __syncthreads();
@@ -319,12 +278,12 @@ __global__ __launch_bounds__(A5_THREADS, 1) void kf_attn_fwd5_kernel(
 #pragma unroll
         for (int j = 0; j < 4; ++j)
           q4[j] = kf_f32_to_bf16(oacc[dt][qh][rq * 4 + j] * inv_l);
-        *reinterpret_cast<kf_short4v5*>(o + obase + d0) =
-            *reinterpret_cast<kf_short4v5*>(q4);
+        *reinterpret_cast<kf_short4*>(o + obase + d0) =
+            *reinterpret_cast<kf_short4*>(q4);
       }
     if (hi == 0)
       lse[(b * Hq + hq) * (int64_t)S + qrow_g] =
-          m_run[qh] * A5_LN2 + __logf(l_run[qh]);
+          m_run[qh] * KF_LN2 + __logf(l_run[qh]);
   }
 }
 

@@ -14,7 +14,9 @@
 
 #define KF_WAVE 64
 
-#define KF_EXPORT extern "C" __attribute__((visibility("default")))
+// KF_EXPORT and the prototype of every exported entry point. Included here so
+// that no kernel file can define or call an entry point without seeing it.
+#include "kf_ops.h"
 
 // Vector aliases for wide loads/stores (guide G13: always vectorize bf16).
 typedef short kf_short4 __attribute__((ext_vector_type(4)));
