@@ -116,6 +116,11 @@ class RMSNorm(nn.Module):
     def forward(self, x):
         return ops.rms_norm(x, self.weight, self.eps)
 
+    def forward_residual(self, x):
+        """(norm(x), x): the returned x is the residual input, so that both
+        gradients of x meet in this norm's backward kernel."""
+        return ops.rms_norm_residual(x, self.weight, self.eps)
+
 
 class MoEMLP(nn.Module):
     """Top-k gated mixture of SwiGLU experts (replaces the dense MLP when
@@ -241,7 +246,13 @@ class LlamaBlock(nn.Module):
     def forward(self, x, cos, sin, pos_offset: int = 0, kv_cache=None):
         cfg = self.cfg
         B, S, h = x.shape
-        nx = self.attn_norm(x)
+        # dense non-TP blocks take the residual input back from the norm
+        # (ops.rms_norm_residual); TP and MoE keep the plain norm
+        res = self.tp is None and self.moe is None
+        if res:
+            nx, x = self.attn_norm.forward_residual(x)
+        else:
+            nx = self.attn_norm(x)
         if self.tp:
             nx = tpmod.copy_to(nx, self.tp)
         qkv = F.linear(nx, self.wqkv.weight)
@@ -300,7 +311,8 @@ class LlamaBlock(nn.Module):
                         self.wo.weight.t()).view(B, S, h)
         if self.moe is not None:
             return x + self.moe(self.mlp_norm(x))
-        y = ops.swiglu(F.linear(self.mlp_norm(x), self.w13.weight))
+        ny, x = self.mlp_norm.forward_residual(x)
+        y = ops.swiglu(F.linear(ny, self.w13.weight))
         return torch.addmm(x.view(-1, h), y.view(B * S, cfg.ffn_dim),
                            self.w2.weight.t()).view(B, S, h)
 

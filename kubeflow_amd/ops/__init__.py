@@ -30,6 +30,7 @@ __all__ = [
     "cross_entropy", "fused_adamw", "rope_cos_sin", "native_available",
     "masked_attention",
     "swiglu", "fused_qkv_attention",
+    "rms_norm_residual", "grad_norm", "step_tail_enabled",
 ]
 
 rope_cos_sin = reference.rope_cos_sin
@@ -115,6 +116,75 @@ def rms_norm(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-5):
     if _use_native(x):
         return _RMSNormHip.apply(x, weight, eps)
     return reference.rms_norm(x, weight, eps)
+
+
+def _norm_res_enabled() -> bool:
+    """KF_NORM_RES=0: bisection switch — rms_norm_residual composes rms_norm
+    with a pass-through x, and autograd sums the two gradients of x with its
+    own add kernel."""
+    return os.environ.get("KF_NORM_RES", "1") != "0"
+
+
+class _RMSNormResHip(torch.autograd.Function):
+    """RMSNorm that also hands its input back: (y, x). A block's x feeds the
+    norm and the residual add; routing the residual branch through this
+    node brings both gradients of x to one backward, which adds the
+    residual's in the store of kf_rmsnorm_bwd_res instead of leaving the sum
+    to a separate bf16 add pass over [rows, cols]."""
+
+    @staticmethod
+    def forward(ctx, x, weight, eps):
+        lib = _backend.require()
+        shape = x.shape
+        x2 = x.contiguous().view(-1, shape[-1])
+        rows, cols = x2.shape
+        y = torch.empty_like(x2)
+        rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+        _backend.check(
+            lib.kf_rmsnorm_fwd(_p(y), _fp(rstd), _p(x2), _p(weight), rows,
+                               cols, float(eps), _stream()), "rmsnorm_fwd")
+        ctx.save_for_backward(x2, weight, rstd)
+        ctx.shape = shape
+        ctx.set_materialize_grads(False)
+        return y.view(shape), x
+
+    @staticmethod
+    def backward(ctx, dy, dxr):
+        if dy is None:  # only the pass-through was used
+            return dxr, None, None
+        lib = _backend.require()
+        x2, weight, rstd = ctx.saved_tensors
+        rows, cols = x2.shape
+        dy2 = dy.contiguous().view(rows, cols)
+        dx = torch.empty_like(x2)
+        dw = torch.empty_like(weight)
+        dw_part = torch.zeros(cols, dtype=torch.float32, device=x2.device)
+        if (dxr is not None and dxr.is_contiguous()
+                and dxr.dtype == dx.dtype and dxr.data_ptr() % 16 == 0):
+            _backend.check(
+                lib.kf_rmsnorm_bwd_res(_p(dx), _p(dw), _fp(dw_part), _p(dy2),
+                                       _p(x2), _p(weight), _fp(rstd),
+                                       _p(dxr), rows, cols, _stream()),
+                "rmsnorm_bwd_res")
+            return dx.view(ctx.shape), dw, None
+        _backend.check(
+            lib.kf_rmsnorm_bwd(_p(dx), _p(dw), _fp(dw_part), _p(dy2), _p(x2),
+                               _p(weight), _fp(rstd), rows, cols, _stream()),
+            "rmsnorm_bwd")
+        dx = dx.view(ctx.shape)
+        return (dx if dxr is None else dx + dxr), dw, None
+
+
+def rms_norm_residual(x: torch.Tensor, weight: torch.Tensor,
+                      eps: float = 1e-5):
+    """(rms_norm(x), x) for a pre-norm residual block: use the returned x,
+    not the argument, as the residual input. Values are rms_norm's; on the
+    GPU the backward makes one kernel call for both gradients of x."""
+    if _use_native(x):
+        if _norm_res_enabled():
+            return _RMSNormResHip.apply(x, weight, eps)
+        return _RMSNormHip.apply(x, weight, eps), x
+    return reference.rms_norm(x, weight, eps), x
 
 
 # ------------------------------------------------------------------ RoPE --
@@ -949,22 +1019,82 @@ def cross_entropy(logits: torch.Tensor, targets: torch.Tensor,
 
 # ----------------------------------------------------------- Fused AdamW --
 
+WD_GROUP = 64  # elements per wd_groups byte (KF_WD_GROUP in adamw.hip)
+
+
+def step_tail_enabled() -> bool:
+    """KF_STEP_TAIL=0: bisection switch — the trainer's step tail runs as
+    torch vector_norm, grad.mul_(scale) and kf_adamw with the fp32 mask
+    instead of kf_grad_sumsq and one kf_adamw_clip."""
+    return os.environ.get("KF_STEP_TAIL", "1") != "0"
+
+
+def grad_norm(grad: torch.Tensor) -> torch.Tensor:
+    """L2 norm of a flat gradient buffer as a 0-dim fp32 tensor on its
+    device, without a host sync. bf16 GPU buffers take kf_grad_sumsq: one
+    streaming read, fp32 partial per block, fp64 final sum, no atomics (the
+    same buffer gives the same bits)."""
+    if (grad.is_cuda and _backend.native_enabled()
+            and grad.dtype == torch.bfloat16 and grad.is_contiguous()
+            and grad.data_ptr() % 16 == 0):
+        lib = _backend.require()
+        n = grad.numel()
+        out = torch.empty(1, dtype=torch.float32, device=grad.device)
+        parts = torch.empty(int(lib.kf_grad_sumsq_nparts(n)),
+                            dtype=torch.float32, device=grad.device)
+        _backend.check(
+            lib.kf_grad_sumsq(_fp(out), _fp(parts), _p(grad), n, _stream()),
+            "grad_sumsq")
+        return out.view(())
+    return torch.linalg.vector_norm(grad, dtype=torch.float32)
+
+
 def fused_adamw(p16: torch.Tensor, p32: torch.Tensor, grad: torch.Tensor,
                 m: torch.Tensor, v: torch.Tensor,
                 wd_mask: Optional[torch.Tensor], lr: float, beta1: float,
-                beta2: float, eps: float, weight_decay: float, step: int):
+                beta2: float, eps: float, weight_decay: float, step: int,
+                wd_groups: Optional[torch.Tensor] = None,
+                gscale: Optional[torch.Tensor] = None):
     """One fused update over a flat bf16 parameter shard + fp32 state.
 
     p16/grad bf16 [N]; p32/m/v fp32 [N]; wd_mask fp32 {0,1} [N] or None.
+
+    wd_groups: uint8 {0,1} [ceil(N / 64)], one byte per 64 elements, in place
+    of wd_mask (FlatParamSpace.build_wd_groups). gscale: 1-element fp32
+    tensor holding float(bf16(clip scale)); the gradient is scaled as
+    grad.mul_(scale.to(bf16)) would, inside the update, and `grad` holds the
+    scaled values afterwards. Either one selects kf_adamw_clip on the GPU.
     """
+    if wd_mask is not None and wd_groups is not None:
+        raise ValueError("fused_adamw: pass wd_mask or wd_groups, not both")
     if p16.is_cuda and _backend.native_enabled():
         lib = _backend.require()
+        if wd_groups is None and gscale is None:
+            _backend.check(
+                lib.kf_adamw(_p(p16), _fp(p32), _p(grad), _fp(m), _fp(v),
+                             _fp(wd_mask), p16.numel(), lr, beta1, beta2, eps,
+                             weight_decay, step, _stream()), "adamw")
+            return
+        n = p16.numel()
+        if wd_groups is not None and (
+                wd_groups.dtype != torch.uint8
+                or wd_groups.numel() * WD_GROUP < n):
+            raise ValueError("fused_adamw: wd_groups must be uint8 with one "
+                             f"entry per {WD_GROUP} elements")
+        if gscale is not None and (gscale.dtype != torch.float32
+                                   or gscale.numel() != 1):
+            raise ValueError("fused_adamw: gscale must be one fp32 element")
         _backend.check(
-            lib.kf_adamw(_p(p16), _fp(p32), _p(grad), _fp(m), _fp(v),
-                         _fp(wd_mask), p16.numel(), lr, beta1, beta2, eps,
-                         weight_decay, step, _stream()), "adamw")
+            lib.kf_adamw_clip(_p(p16), _fp(p32), _p(grad), _fp(m), _fp(v),
+                              _fp(wd_mask), _p(wd_groups), _fp(gscale), n,
+                              lr, beta1, beta2, eps, weight_decay, step,
+                              _stream()), "adamw_clip")
         return
     # reference path (CPU tests)
+    if gscale is not None:
+        grad.mul_(gscale.reshape(()).to(grad.dtype))
+    if wd_groups is not None:
+        wd_mask = wd_groups.float().repeat_interleave(WD_GROUP)[:p16.numel()]
     g32 = grad.float()
     m.mul_(beta1).add_(g32, alpha=1 - beta1)
     v.mul_(beta2).addcmul_(g32, g32, value=1 - beta2)

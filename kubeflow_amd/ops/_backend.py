@@ -63,7 +63,7 @@ def require():
 
 # The C ABI of libkfops.so as data: entry point -> argtypes, one entry per
 # prototype in csrc/kf_ops.h (tests/test_ops_abi.py checks the two against
-# each other). Every entry point returns hipError_t as int, except the two
+# each other). Every entry point returns hipError_t as int, except the
 # *_nparts helpers, which return a count as int64.
 _P, _F = ctypes.c_void_p, ctypes.c_float
 _I64, _I32 = ctypes.c_int64, ctypes.c_int
@@ -86,6 +86,7 @@ SIGNATURES: dict[str, list] = {
     "kf_rmsnorm_fwd": [_P, _FP, _P, _P, _I64, _I64, _F, _P],
     "kf_rmsnorm_bwd_nparts": [_I64],
     "kf_rmsnorm_bwd": [_P, _P, _FP, _P, _P, _P, _FP, _I64, _I64, _P],
+    "kf_rmsnorm_bwd_res": [_P, _P, _FP, _P, _P, _P, _FP, _P, _I64, _I64, _P],
     "kf_layernorm_fwd": [_P, _FP, _FP, _P, _P, _P, _I64, _I64, _F, _P],
     "kf_layernorm_bwd_nparts": [_I64],
     "kf_layernorm_bwd": [_P, _P, _P, _FP, _P, _P, _P, _FP, _FP, _I64, _I64,
@@ -95,6 +96,11 @@ SIGNATURES: dict[str, list] = {
     "kf_swiglu_bwd": [_P, _P, _P, _I64, _I64, _P],
     "kf_adamw": [_P, _FP, _P, _FP, _FP, _FP, _I64, _F, _F, _F, _F, _F, _I64,
                  _P],
+    # p16, p32, g, m, v, wd_mask, wd_groups, gscale, n, lr..wd, step, stream
+    "kf_adamw_clip": [_P, _FP, _P, _FP, _FP, _FP, _P, _FP, _I64, _F, _F, _F,
+                      _F, _F, _I64, _P],
+    "kf_grad_sumsq_nparts": [_I64],
+    "kf_grad_sumsq": [_FP, _FP, _P, _I64, _P],
     "kf_ce_fwd": [_FP, _FP, _P, _PI64, _I64, _I64, _I64, _P],
     "kf_ce_bwd": [_P, _P, _FP, _PI64, _FP, _I64, _I64, _I64, _P],
     "kf_skinny_gemm": [_P, _P, _P, _P, _FP, _F] + [_I64] * 7 + [_P],
@@ -125,7 +131,8 @@ SIGNATURES: dict[str, list] = {
     "kf_attn64_bwd": _BWD_HEAD + [_I64, _I64, _F, _I32, _I64, _P],
     "kf_attn_decode": [_P] * 6 + [_PI32, _PI32] + [_I64] * 6 + [_F, _P],
 }
-_RETURNS_INT64 = ("kf_rmsnorm_bwd_nparts", "kf_layernorm_bwd_nparts")
+_RETURNS_INT64 = ("kf_rmsnorm_bwd_nparts", "kf_layernorm_bwd_nparts",
+                  "kf_grad_sumsq_nparts")
 
 
 def _configure(lib: ctypes.CDLL) -> None:

@@ -24,6 +24,10 @@ KF_EXPORT int64_t kf_rmsnorm_bwd_nparts(int64_t rows);
 KF_EXPORT int kf_rmsnorm_bwd(void* dx, void* dw, float* dw_acc, const void* dy,
     const void* x, const void* w, const float* rstd, int64_t rows,
     int64_t cols, void* stream);
+// kf_rmsnorm_bwd plus dres [rows, cols] bf16 (may be null), added to dx
+KF_EXPORT int kf_rmsnorm_bwd_res(void* dx, void* dw, float* dw_acc,
+    const void* dy, const void* x, const void* w, const float* rstd,
+    const void* dres, int64_t rows, int64_t cols, void* stream);
 KF_EXPORT int kf_layernorm_fwd(void* y, float* mu, float* rstd, const void* x,
     const void* w, const void* b, int64_t rows, int64_t cols, float eps,
     void* stream);
@@ -44,6 +48,18 @@ KF_EXPORT int kf_swiglu_bwd(void* dh, const void* dy, const void* h, int64_t T,
 KF_EXPORT int kf_adamw(void* p16, float* p32, const void* g, float* m,
     float* v, const float* wd_mask, int64_t n, float lr, float b1, float b2,
     float eps, float wd, int64_t step, void* stream);
+// step tail: kf_adamw with the clip scale (device scalar gscale, may be null;
+// g is rewritten with the scaled gradient when *gscale != 1) and a uint8
+// per-64-element decay mask wd_groups (may be null; not both masks);
+// kf_grad_sumsq writes sqrt(sum g^2) to out[0] through a partials buffer of
+// kf_grad_sumsq_nparts(n) floats
+KF_EXPORT int kf_adamw_clip(void* p16, float* p32, void* g, float* m,
+    float* v, const float* wd_mask, const void* wd_groups,
+    const float* gscale, int64_t n, float lr, float b1, float b2, float eps,
+    float wd, int64_t step, void* stream);
+KF_EXPORT int64_t kf_grad_sumsq_nparts(int64_t n);
+KF_EXPORT int kf_grad_sumsq(float* out, float* partials, const void* g,
+    int64_t n, void* stream);
 KF_EXPORT int kf_ce_fwd(float* loss_sum, float* lse, const void* logits,
     const int64_t* targets, int64_t T, int64_t V, int64_t ignore_index,
     void* stream);

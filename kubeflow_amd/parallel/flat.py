@@ -73,6 +73,20 @@ class FlatParamSpace:
                 mask[off:off + n].fill_(1.0)
         return mask
 
+    def build_wd_groups(self, decay_dim_ge: int = 2) -> torch.Tensor:
+        """build_wd_mask in compact form: uint8 {0,1}, one entry per ALIGN
+        elements (numel / ALIGN entries, 1/256 of the fp32 mask's bytes).
+        Every slice starts on an ALIGN boundary, so a group never spans two
+        parameters; a decayed slice's trailing padding shares its group's 1,
+        which changes nothing: padding holds p = g = m = v = 0 and updates
+        to 0 under either value."""
+        groups = torch.zeros(self.numel // ALIGN, dtype=torch.uint8,
+                             device=self.device)
+        for (off, n), p in zip(self.slices, self.params):
+            if p.dim() >= decay_dim_ge:
+                groups[off // ALIGN:(off + _aligned(n)) // ALIGN].fill_(1)
+        return groups
+
     def state_dict_tensors(self):
         """(name, view) pairs in registration order for checkpointing."""
         return list(zip(self.names, (self.data[o:o + n] for o, n in self.slices)))

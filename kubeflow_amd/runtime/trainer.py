@@ -67,6 +67,8 @@ class Trainer:
             self.v = torch.zeros_like(self.p32)
             self.wd_mask = (self.flat.build_wd_mask() if cfg.use_wd_mask
                             else None)
+            self.wd_groups = (self.flat.build_wd_groups()
+                              if cfg.use_wd_mask else None)
             self.step_num = 0
             return
         if (zero and dist.is_initialized() and dist.get_world_size() > 1
@@ -86,6 +88,14 @@ class Trainer:
                 del full
             else:
                 self.wd_mask = None
+            # the compact mask indexes groups from the shard's start: only
+            # a shard that starts on a group boundary can use it
+            self.wd_groups = None
+            if cfg.use_wd_mask and self.zero.lo % ops.WD_GROUP == 0:
+                g_lo = self.zero.lo // ops.WD_GROUP
+                g_hi = -(-self.zero.hi // ops.WD_GROUP)
+                self.wd_groups = \
+                    self.flat.build_wd_groups()[g_lo:g_hi].clone()
             self.step_num = 0
             return
         if tp_ctx is not None and dp_group is not None \
@@ -105,6 +115,8 @@ class Trainer:
         self.m = torch.zeros_like(self.p32)
         self.v = torch.zeros_like(self.p32)
         self.wd_mask = self.flat.build_wd_mask() if cfg.use_wd_mask else None
+        self.wd_groups = (self.flat.build_wd_groups() if cfg.use_wd_mask
+                          else None)
         self.step_num = 0
 
     # ------------------------------------------------------------ schedule
@@ -150,42 +162,65 @@ class Trainer:
         return loss.detach()
 
     # ---------------------------------------------------------- optimizer
+    def _fused_tail(self, grad: torch.Tensor) -> bool:
+        """Whether this step's tail folds the clip multiply and the compact
+        decay mask into one kf_adamw_clip (bf16 gradients on the GPU; read
+        per step, KF_STEP_TAIL=0 selects the separate passes)."""
+        return (ops.step_tail_enabled() and grad.is_cuda
+                and grad.dtype == torch.bfloat16 and ops.native_available())
+
+    def _update(self, p16, grad, scale, fused: bool):
+        """Clip by `scale` (0-dim tensor or None) and run fused AdamW. The
+        fused tail hands the kernel float(bf16(scale)) and lets it scale, and
+        write back, the gradients it reads anyway; `grad` ends the step
+        holding the same bits either way."""
+        cfg = self.cfg
+        gscale = None
+        if scale is not None:
+            if fused:
+                gscale = scale.to(grad.dtype).float().reshape(1)
+            else:
+                grad.mul_(scale.to(grad.dtype))
+        mask, groups = self.wd_mask, None
+        if fused and self.wd_groups is not None:
+            mask, groups = None, self.wd_groups
+        self.step_num += 1
+        lr = self.lr_at(self.step_num - 1)
+        ops.fused_adamw(p16, self.p32, grad, self.m, self.v, mask, lr,
+                        cfg.beta1, cfg.beta2, cfg.eps, cfg.weight_decay,
+                        self.step_num, wd_groups=groups, gscale=gscale)
+
     def _clip_and_update(self):
         """Shared grad-clip + fused-AdamW tail of a step (grads already in
         the flat buffer, comm done)."""
         cfg = self.cfg
+        grad = self.flat.grad
+        fused = self._fused_tail(grad)
+        scale = None
         if cfg.grad_clip > 0:
             comm = next((c for c in (self.tp, self.pp, self.ep)
                          if c is not None), None)
             if comm is not None:
                 gnorm = comm.global_grad_norm(self.flat)
+            elif fused:
+                gnorm = ops.grad_norm(grad)
             else:
-                gnorm = torch.linalg.vector_norm(self.flat.grad,
-                                                 dtype=torch.float32)
+                gnorm = torch.linalg.vector_norm(grad, dtype=torch.float32)
             scale = (cfg.grad_clip / (gnorm + 1e-6)).clamp(max=1.0)
-            self.flat.grad.mul_(scale.to(self.flat.grad.dtype))
             self.last_grad_norm = gnorm
-        self.step_num += 1
-        lr = self.lr_at(self.step_num - 1)
-        ops.fused_adamw(self.flat.data, self.p32, self.flat.grad, self.m,
-                        self.v, self.wd_mask, lr, cfg.beta1, cfg.beta2,
-                        cfg.eps, cfg.weight_decay, self.step_num)
+        self._update(self.flat.data, grad, scale, fused)
 
     def _zero_update(self):
         """ZeRO-1 step tail: averaged grad shard -> clip -> shard AdamW ->
         param all-gather."""
         cfg = self.cfg
         gs = self.zero.reduce_scatter_grads()
+        scale = None
         if cfg.grad_clip > 0:
             gnorm = self.zero.global_grad_norm(gs)
             scale = (cfg.grad_clip / (gnorm + 1e-6)).clamp(max=1.0)
-            gs.mul_(scale.to(gs.dtype))
             self.last_grad_norm = gnorm
-        self.step_num += 1
-        lr = self.lr_at(self.step_num - 1)
-        ops.fused_adamw(self.zero.data_shard(), self.p32, gs, self.m,
-                        self.v, self.wd_mask, lr, cfg.beta1, cfg.beta2,
-                        cfg.eps, cfg.weight_decay, self.step_num)
+        self._update(self.zero.data_shard(), gs, scale, self._fused_tail(gs))
         self.zero.all_gather_params()
 
     # ---------------------------------------------------------- checkpoint
