@@ -11,6 +11,7 @@ through the hand-written HIP layernorm kernel.
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -32,6 +33,9 @@ class BertConfig:
     n_classes: int = 2
     norm_eps: float = 1e-12
     init_std: float = 0.02
+    # right-padded batches: when set and the caller passes neither kv_len nor
+    # seq_lens, each row's length is its count of non-pad tokens
+    pad_token_id: Optional[int] = None
 
 
 def bert_base() -> BertConfig:
@@ -75,7 +79,7 @@ class BertLayer(nn.Module):
         self.fc2 = nn.Linear(cfg.ffn_dim, h)
         self.ln2 = KfLayerNorm(h, eps=cfg.norm_eps)
 
-    def forward(self, x, kv_len=None):
+    def forward(self, x, kv_len=None, seq_lens=None):
         cfg = self.cfg
         B, S, _ = x.shape
         q, k, v = self.wqkv(x).split(cfg.n_heads * cfg.head_dim, dim=-1)
@@ -84,7 +88,11 @@ class BertLayer(nn.Module):
         v = v.view(B, S, cfg.n_heads, cfg.head_dim)
         if kv_len is not None and kv_len >= S:
             kv_len = None
-        if cfg.head_dim == 64:
+        if seq_lens is not None:
+            # one length per row; rows past it are padding on both axes (with
+            # head dim 128 on the GPU the op raises: no per-sequence mask)
+            o = ops.flash_attention(q, k, v, causal=False, seq_lens=seq_lens)
+        elif cfg.head_dim == 64:
             # one kernel family for training and serving: the padded-length
             # mask is an argument, and it is differentiable
             o = ops.flash_attention(q, k, v, causal=False, kv_len=kv_len)
@@ -125,12 +133,33 @@ class BertClassifier(nn.Module):
                 mod.weight.fill_(1.0)
                 mod.bias.zero_()
 
-    def forward(self, tokens, targets=None, kv_len=None):
+    def forward(self, tokens, targets=None, kv_len=None, seq_lens=None):
+        """kv_len: one padded length for the whole batch. seq_lens: one
+        length per row ([B], right-padded batch); a list or CPU tensor is
+        validated by the attention op, an int32 tensor on the tokens' device
+        is used as is. With cfg.pad_token_id set and neither given, the
+        lengths are derived from the tokens on the device (no host sync)."""
         B, S = tokens.shape
+        if (seq_lens is None and kv_len is None
+                and self.cfg.pad_token_id is not None):
+            seq_lens = (tokens != self.cfg.pad_token_id).sum(1).clamp_min(
+                1).int()
+        elif seq_lens is not None and not (
+                isinstance(seq_lens, torch.Tensor)
+                and seq_lens.device == tokens.device
+                and seq_lens.dtype == torch.int32):
+            host = torch.as_tensor(seq_lens)
+            if host.shape != (B,) or host.is_floating_point() or \
+                    int(host.min()) < 1 or int(host.max()) > S:
+                raise ValueError(
+                    f"seq_lens must be {B} integers in [1, {S}], got "
+                    f"{host.tolist()}")
+            # validated and moved once, not once per layer
+            seq_lens = host.to(device=tokens.device, dtype=torch.int32)
         pos = torch.arange(S, device=tokens.device)
         x = self.embed_ln(self.tok_embed(tokens) + self.pos_embed(pos))
         for layer in self.layers:
-            x = layer(x, kv_len=kv_len)
+            x = layer(x, kv_len=kv_len, seq_lens=seq_lens)
         logits = self.classifier(x[:, 0])  # [CLS]
         if targets is None:
             return logits

@@ -567,6 +567,111 @@ def _flash_attention64(q, k, v, causal, scale, kv_len):
     return o[:, :S] if pad else o
 
 
+class _FlashAttn64VarlenHip(torch.autograd.Function):
+    """Head-dim-64 family with per-sequence lengths (kf_attn64_*_varlen):
+    rows >= seq_lens[b] are padding on both axes; o and all three gradients
+    are exact zeros there. Non-causal."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, scale, seq_lens):
+        lib = _backend.require()
+        B, S, Hq, D = q.shape
+        Hkv = k.shape[2]
+        qts = _row_stride(q)
+        if qts is None:
+            q = q.contiguous()
+            qts = Hq * D
+        kts = _row_stride(k)
+        if kts is None or _row_stride(v) != kts:
+            k, v = k.contiguous(), v.contiguous()
+            kts = Hkv * D
+        o = torch.empty(B, S, Hq, D, dtype=q.dtype, device=q.device)
+        lse = torch.empty(B, Hq, S, dtype=torch.float32, device=q.device)
+        _backend.check(
+            lib.kf_attn64_fwd_varlen(_p(o), _fp(lse), _p(q), _p(k), _p(v),
+                                     _i32p(seq_lens), B, S, Hq, Hkv, qts,
+                                     kts, float(scale), _stream()),
+            "attn64_fwd_varlen")
+        ctx.save_for_backward(q, k, v, o, lse, seq_lens)
+        ctx.meta = (scale, qts, kts)
+        return o
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _backend.require()
+        q, k, v, o, lse, seq_lens = ctx.saved_tensors
+        scale, qts, kts = ctx.meta
+        B, S, Hq, D = q.shape
+        Hkv = k.shape[2]
+        dout = dout.contiguous()
+        dq = torch.empty(B, S, Hq, D, dtype=q.dtype, device=q.device)
+        dk = torch.empty(B, S, Hkv, D, dtype=k.dtype, device=k.device)
+        dv = torch.empty_like(dk)
+        delta = torch.empty(B, Hq, S, dtype=torch.float32, device=q.device)
+        _backend.check(
+            lib.kf_attn64_bwd_varlen(_p(dq), _p(dk), _p(dv), _p(dout), _p(q),
+                                     _p(k), _p(v), _p(o), _fp(lse),
+                                     _fp(delta), _i32p(seq_lens), B, S, Hq,
+                                     Hkv, qts, kts, float(scale), _stream()),
+            "attn64_bwd_varlen")
+        return dq, dk, dv, None, None
+
+
+def _flash_attention64_varlen(q, k, v, scale, seq_lens):
+    """D == 64 native route with per-sequence lengths: any S (zero-padded to
+    a 128 multiple; the pad rows are past every length, so the lengths need
+    no adjustment and the padded rows come back as zeros and are sliced
+    off)."""
+    if q.dtype != torch.bfloat16:
+        raise ValueError(f"native attention needs bf16 inputs, got {q.dtype}")
+    S = q.shape[1]
+    pad = (128 - S % 128) % 128
+    if pad:
+        q, k, v = _pad_rows(q, pad), _pad_rows(k, pad), _pad_rows(v, pad)
+    o = _FlashAttn64VarlenHip.apply(q, k, v, scale, seq_lens)
+    return o[:, :S] if pad else o
+
+
+def _seq_lens_arg(seq_lens, q):
+    """seq_lens as flash_attention takes it -> int32 [B] on q's device. An
+    int32 tensor already there is used as is (no host sync, no validation:
+    the kernels clamp); anything else is checked on the host and moved."""
+    B, S = q.shape[0], q.shape[1]
+    if (isinstance(seq_lens, torch.Tensor) and seq_lens.device == q.device
+            and seq_lens.dtype == torch.int32 and q.is_cuda):
+        if seq_lens.shape != (B,):
+            raise ValueError(
+                f"seq_lens must have shape [{B}], got {tuple(seq_lens.shape)}")
+        return seq_lens.contiguous()
+    host = torch.as_tensor(seq_lens).detach().cpu()
+    if host.shape != (B,) or host.is_floating_point():
+        raise ValueError(
+            f"seq_lens must be {B} integers, got shape {tuple(host.shape)} "
+            f"dtype {host.dtype}")
+    if int(host.min()) < 1 or int(host.max()) > S:
+        raise ValueError(
+            f"seq_lens must be in [1, {S}], got {host.tolist()}")
+    return host.to(device=q.device, dtype=torch.int32)
+
+
+def _sdpa_ref_varlen(q, k, v, scale, seq_lens):
+    """Reference math per sequence (differentiable): reference.sdpa on the
+    [:L] slices, scattered into zeros — the kernels' zero-row semantics, so
+    o and every gradient are exactly zero past each length."""
+    lens = seq_lens.tolist()
+    S = q.shape[1]
+    rows = []
+    for b, L in enumerate(lens):
+        L = min(max(int(L), 1), S)
+        ob = reference.sdpa(q[b:b + 1, :L].transpose(1, 2),
+                            k[b:b + 1, :L].transpose(1, 2),
+                            v[b:b + 1, :L].transpose(1, 2),
+                            causal=False, scale=scale).transpose(1, 2)
+        rows.append(torch.cat(
+            [ob, ob.new_zeros(1, S - L, ob.shape[2], ob.shape[3])], dim=1))
+    return torch.cat(rows, dim=0)
+
+
 def _sdpa_ref(q, k, v, causal, scale, kv_len):
     """Reference math in bshd (differentiable): k/v sliced to kv_len, so
     autograd yields zero gradient rows past it."""
@@ -693,11 +798,23 @@ def masked_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
 
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                     causal: bool = True, scale: Optional[float] = None,
-                    kv_len: Optional[int] = None):
+                    kv_len: Optional[int] = None, seq_lens=None):
     """bshd layout: q [B,S,Hq,D], k/v [B,S,Hkv,D] -> o [B,S,Hq,D].
 
     kv_len (non-causal only): key/value rows >= kv_len are padding and are
     never attended; their gradients are zero. Works under autograd.
+
+    seq_lens (non-causal only, not together with kv_len): one length per
+    batch row, shape [B] — the right-padded batch. Rows >= seq_lens[b] of
+    sequence b are padding on both axes: its queries attend keys
+    [0, seq_lens[b]), and o and dq/dk/dv rows past the length are exact
+    zeros whatever dout holds there. An int32 tensor on q's device is used as
+    is, with no host sync and no validation (the kernels clamp each length
+    into [1, S]); a CPU tensor or a list is checked (1 <= len <= S) and
+    moved. Native at D == 64 (kf_attn64_*_varlen: the work is
+    sum_b len_b^2, padded blocks and tiles are skipped, not masked); D == 128
+    on the GPU raises. Off the GPU and under KF_ATTN_D64=0 the reference
+    math runs per sequence with the same zero-row semantics.
 
     The CDNA4 kernels tile q in 128-row blocks. D == 128: causal sequences
     are zero-padded to a 128 multiple here (padded key rows are causally
@@ -718,8 +835,24 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         if not 1 <= kv_len <= k.shape[1]:
             raise ValueError(
                 f"kv_len must be in [1, {k.shape[1]}], got {kv_len}")
+    if seq_lens is not None:
+        if causal:
+            raise ValueError("flash_attention: seq_lens is non-causal only")
+        if kv_len is not None:
+            raise ValueError(
+                "flash_attention: pass kv_len or seq_lens, not both")
+        seq_lens = _seq_lens_arg(seq_lens, q)
     if _use_native(q):
         _check_head_dim(D)
+        if seq_lens is not None:
+            if D != 64:
+                raise ValueError(
+                    "flash_attention: seq_lens needs head_dim 64 on the "
+                    "native path; the head_dim 128 kernels have no "
+                    "per-sequence mask")
+            if _attn64_enabled():
+                return _flash_attention64_varlen(q, k, v, scale, seq_lens)
+            return _sdpa_ref_varlen(q, k, v, scale, seq_lens)
         if D == 64:
             if _attn64_enabled():
                 return _flash_attention64(q, k, v, causal, scale, kv_len)
@@ -742,6 +875,8 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
             v = torch.cat([v, zk], dim=1)
             return _FlashAttnHip.apply(q, k, v, causal, scale)[:, :S]
         return _FlashAttnHip.apply(q, k, v, causal, scale)
+    if seq_lens is not None:
+        return _sdpa_ref_varlen(q, k, v, scale, seq_lens)
     return _sdpa_ref(q, k, v, causal, scale, kv_len)
 
 

@@ -129,6 +129,10 @@ SIGNATURES: dict[str, list] = {
     "kf_attn64_fwd": [_P, _FP, _P, _P, _P] + [_I64] * 6 + [_F, _I32, _I64,
                                                            _P],
     "kf_attn64_bwd": _BWD_HEAD + [_I64, _I64, _F, _I32, _I64, _P],
+    # ..., seq_lens, B, S, Hq, Hkv, qts, kts, scale, stream
+    "kf_attn64_fwd_varlen": [_P, _FP, _P, _P, _P, _PI32] + [_I64] * 6 +
+                            [_F, _P],
+    "kf_attn64_bwd_varlen": _BWD_HEAD[:10] + [_PI32] + [_I64] * 6 + [_F, _P],
     "kf_attn_decode": [_P] * 6 + [_PI32, _PI32] + [_I64] * 6 + [_F, _P],
 }
 _RETURNS_INT64 = ("kf_rmsnorm_bwd_nparts", "kf_layernorm_bwd_nparts",

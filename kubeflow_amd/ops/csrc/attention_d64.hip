@@ -1,5 +1,6 @@
 // attention_d64.hip — head-dim-64 flash attention, forward + backward (bf16,
-// GQA, optional kv_len mask) for CDNA4. The BERT-base family: 12 heads x 64.
+// GQA, optional kv_len or per-sequence-length mask) for CDNA4. The BERT-base
+// family: 12 heads x 64.
 //
 // Contract (every entry point):
 //   q/o/dq/dout [B,S,Hq,64], k/v/dk/dv [B,S,Hkv,64] bf16 (bshd); lse/delta
@@ -42,12 +43,34 @@
 //   dq    177 VGPRs, scratch 0, LDS 24,576 B, 2 waves/SIMD
 //   dkv   245 VGPRs, scratch 0, LDS 33,280 B, 2 waves/SIMD
 // (4 waves/SIMD on fwd/dq spilled 104 / 224 B per lane.)
+// VARLEN instantiations (per-sequence lengths, below):
+//   fwd   165 VGPRs, scratch 0, LDS 16,384 B, 3 waves/SIMD
+//   dq    189 VGPRs, scratch 0, LDS 24,576 B, 2 waves/SIMD
+//   dkv   211 VGPRs, scratch 0, LDS 33,280 B, 2 waves/SIMD
 //
 // kv_len: tiles wholly past kv_len are neither loaded nor computed (the
 // tile loops end at ceil(kv_len/64); dK/dV blocks wholly past it write
 // zeros and exit); the per-element mask runs only on 32-row sub-tiles that
 // straddle kv_len or the causal diagonal; dK/dV rows >= kv_len are stored
 // as exact zeros.
+//
+// Per-sequence lengths (kf_attn64_fwd_varlen / kf_attn64_bwd_varlen, the
+// <true> instantiations of the three MFMA kernels; non-causal only):
+// seq_lens is a device int32 [B] and L = clamp(seq_lens[b], 1, S) is read by
+// every block (b = blockIdx.z is block-uniform), so no content of seq_lens
+// can cause an out-of-range access or an empty softmax row. Rows >= L are
+// padding on BOTH axes: k/v rows >= L never enter the math (the kv_len code
+// above with kv_len = L), and o, dq, dk, dv rows >= L are stored as exact
+// zeros. Skipped, not masked: a fwd/dQ block with qt*128 >= L stores its
+// zeros and returns before any K/V load; in the straddling block, waves
+// wholly past L run no MFMA and only take part in staging and the barriers;
+// the fused dK/dV pass ends its q-tile loop per head at ceil(L/64). Padded q
+// rows inside a live 32-row wave or the last dK/dV q tile are killed through
+// lse: the forward stores lse = +inf for rows >= L, so P = exp2(s*scale2 -
+// lse2) and with it dS are exactly 0 for those rows in dQ and dK/dV, whatever
+// finite values q and dout hold there, without a second per-element mask on
+// the q axis (the dK/dV kernel has no registers for one). o = 0 there gives
+// delta = 0, so the delta pass is shared unchanged.
 
 #include "kf_attn_common.h"
 
@@ -138,12 +161,28 @@ __device__ __forceinline__ void kf_store_row64(unsigned short* dst,
     }
 }
 
+// The length argument of the MFMA kernels: the scalar kv_len, or, in the
+// VARLEN instantiations, the device array of per-sequence lengths. Keeping it
+// one parameter of a dependent type leaves the scalar instantiations with the
+// parameter list and the code they had before VARLEN existed.
+template <bool VARLEN> struct kf_len_arg { typedef int type; };
+template <> struct kf_len_arg<true> { typedef const int* type; };
+__device__ __forceinline__ int kf_len(int kv_len, int64_t, int) {
+  return kv_len;
+}
+// seq_lens[b] clamped into [1, S] as it is read: memory safety, not validation
+__device__ __forceinline__ int kf_len(const int* seq_lens, int64_t b, int S) {
+  return min(max(seq_lens[b], 1), S);
+}
+
 // ---------------------------------------------------------------- forward --
+template <bool VARLEN>
 __global__ __launch_bounds__(A6_THREADS, 3) void kf_attn64_fwd_kernel(
     unsigned short* __restrict__ o, float* __restrict__ lse,
     const unsigned short* __restrict__ q, const unsigned short* __restrict__ k,
     const unsigned short* __restrict__ v, int S, int Hq, int Hkv, int64_t qts,
-    int64_t kts, float scale, int causal, int kv_len) {
+    int64_t kts, float scale, int causal_arg,
+    typename kf_len_arg<VARLEN>::type len_arg) {
   __shared__ __attribute__((aligned(16))) unsigned char k_lds[A6_TILEB];
   __shared__ __attribute__((aligned(16))) unsigned char vt_lds[A6_TILEB];
 
@@ -156,6 +195,21 @@ __global__ __launch_bounds__(A6_THREADS, 3) void kf_attn64_fwd_kernel(
   const int wave_qmin = qt * A6_BT + w * 32;
   const int qrow_g = wave_qmin + l31;
   const float scale2 = scale * KF_LOG2E;
+  // VARLEN is non-causal; the length bounds the q axis as well as the kv axis
+  const int causal = VARLEN ? 0 : causal_arg;
+  const int kv_len = kf_len(len_arg, b, S);
+
+  if constexpr (VARLEN) {
+    if (qt * A6_BT >= kv_len) {  // block-uniform: all rows padding
+      const kf_f32x16 zero[2] = {kf_f32x16{0.f}, kf_f32x16{0.f}};
+      kf_store_row64(o + ((b * S + qrow_g) * (int64_t)Hq + hq) * A6_D, zero,
+                     hi, 0.f);
+      if (hi == 0) lse[(b * Hq + hq) * (int64_t)S + qrow_g] = INFINITY;
+      return;
+    }
+  }
+  // waves wholly past the length only help staging (wave-uniform)
+  const bool wave_live = !VARLEN || wave_qmin < kv_len;
 
   // persistent Q B-fragments: B[k=d][n=q], this lane holds q row qrow_g
   kf_bf16x8 qfrag[4];
@@ -192,6 +246,8 @@ __global__ __launch_bounds__(A6_THREADS, 3) void kf_attn64_fwd_kernel(
     for (int mt = 0; mt < 2; ++mt) {
       const int kv_lo = kt * A6_TT + mt * 32;
       if (kv_lo >= kv_lim) continue;  // wave-uniform: fully masked sub-tile
+      if constexpr (VARLEN)
+        if (!wave_live) continue;
       // S^T = mfma(K, Q): rows kv, cols q
       kf_f32x16 st = kf_f32x16{0.f};
       __builtin_amdgcn_s_setprio(1);
@@ -255,6 +311,18 @@ __global__ __launch_bounds__(A6_THREADS, 3) void kf_attn64_fwd_kernel(
     __syncthreads();  // all waves done with the tile before it is overwritten
   }
 
+  if constexpr (VARLEN) {
+    // padded q row: exact zeros, and lse = +inf makes P = exp2(s - lse)
+    // exactly 0 for this row in both backward passes
+    const bool pad = qrow_g >= kv_len;
+    if (pad) oacc[0] = oacc[1] = kf_f32x16{0.f};
+    kf_store_row64(o + ((b * S + qrow_g) * (int64_t)Hq + hq) * A6_D, oacc, hi,
+                   pad ? 0.f : 1.f / l_run);
+    if (hi == 0)
+      lse[(b * Hq + hq) * (int64_t)S + qrow_g] =
+          pad ? INFINITY : m_run * KF_LN2 + __logf(l_run);
+    return;
+  }
   kf_store_row64(o + ((b * S + qrow_g) * (int64_t)Hq + hq) * A6_D, oacc, hi,
                  1.f / l_run);
   if (hi == 0)
@@ -293,12 +361,14 @@ __global__ __launch_bounds__(A6_THREADS) void kf_attn64_delta_kernel(
 //   S^T = mfma(K, Q), dP^T = mfma(V, dO)
 //   dS^T = P^T o (dP^T - delta) * scale           (registers)
 //   dQ^T += mfma(K^T, exch(dS^T))                 K^T from the transposed tile
+template <bool VARLEN>
 __global__ __launch_bounds__(A6_THREADS, 2) void kf_attn64_dq_kernel(
     unsigned short* __restrict__ dq, const unsigned short* __restrict__ q,
     const unsigned short* __restrict__ k, const unsigned short* __restrict__ v,
     const unsigned short* __restrict__ dout, const float* __restrict__ lse,
     const float* __restrict__ delta, int S, int Hq, int Hkv, int64_t qts,
-    int64_t kts, float scale, int causal, int kv_len) {
+    int64_t kts, float scale, int causal_arg,
+    typename kf_len_arg<VARLEN>::type len_arg) {
   __shared__ __attribute__((aligned(16))) unsigned char k_lds[A6_TILEB];
   __shared__ __attribute__((aligned(16))) unsigned char v_lds[A6_TILEB];
   __shared__ __attribute__((aligned(16))) unsigned char kt_lds[A6_TILEB];
@@ -312,6 +382,19 @@ __global__ __launch_bounds__(A6_THREADS, 2) void kf_attn64_dq_kernel(
   const int wave_qmin = qt * A6_BT + w * 32;
   const int qrow_g = wave_qmin + l31;
   const float scale2 = scale * KF_LOG2E;
+  // VARLEN is non-causal; the length bounds the q axis as well as the kv axis
+  const int causal = VARLEN ? 0 : causal_arg;
+  const int kv_len = kf_len(len_arg, b, S);
+
+  if constexpr (VARLEN) {
+    if (qt * A6_BT >= kv_len) {  // block-uniform: all rows padding
+      const kf_f32x16 zero[2] = {kf_f32x16{0.f}, kf_f32x16{0.f}};
+      kf_store_row64(dq + ((b * S + qrow_g) * (int64_t)Hq + hq) * A6_D, zero,
+                     hi, 0.f);
+      return;
+    }
+  }
+  const bool wave_live = !VARLEN || wave_qmin < kv_len;  // wave-uniform
 
   kf_bf16x8 qfrag[4], dofrag[4];
   {
@@ -352,6 +435,8 @@ __global__ __launch_bounds__(A6_THREADS, 2) void kf_attn64_dq_kernel(
     for (int mt = 0; mt < 2; ++mt) {
       const int kv_lo = kt * A6_TT + mt * 32;
       if (kv_lo >= kv_lim) continue;  // wave-uniform skip
+      if constexpr (VARLEN)
+        if (!wave_live) continue;
       kf_f32x16 st = kf_f32x16{0.f}, dpt = kf_f32x16{0.f};
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -398,6 +483,10 @@ __global__ __launch_bounds__(A6_THREADS, 2) void kf_attn64_dq_kernel(
     __syncthreads();
   }
 
+  // padded q rows: lse = +inf from the forward already made every dS 0; the
+  // select keeps the zeros exact whatever dout holds there
+  if constexpr (VARLEN)
+    if (qrow_g >= kv_len) dqacc[0] = dqacc[1] = kf_f32x16{0.f};
   kf_store_row64(dq + ((b * S + qrow_g) * (int64_t)Hq + hq) * A6_D, dqacc, hi,
                  1.f);
 }
@@ -409,13 +498,15 @@ __global__ __launch_bounds__(A6_THREADS, 2) void kf_attn64_dq_kernel(
 //   S = mfma(Q, K), dP = mfma(dO, V)       K/V persistent B-fragments
 //   dV^T += mfma(dO^T, exch(P))            dO^T, Q^T from transposed tiles
 //   dK^T += mfma(Q^T, exch(dS))
+template <bool VARLEN>
 __global__ __launch_bounds__(A6_THREADS, 2) void kf_attn64_dkv_kernel(
     unsigned short* __restrict__ dk, unsigned short* __restrict__ dv,
     const unsigned short* __restrict__ q, const unsigned short* __restrict__ k,
     const unsigned short* __restrict__ v,
     const unsigned short* __restrict__ dout, const float* __restrict__ lse,
     const float* __restrict__ delta, int S, int Hq, int Hkv, int64_t qts,
-    int64_t kts, float scale, int causal, int kv_len) {
+    int64_t kts, float scale, int causal_arg,
+    typename kf_len_arg<VARLEN>::type len_arg) {
   __shared__ __attribute__((aligned(16))) unsigned char q_lds[A6_TILEB];
   __shared__ __attribute__((aligned(16))) unsigned char do_lds[A6_TILEB];
   __shared__ __attribute__((aligned(16))) unsigned char qt_lds[A6_TILEB];
@@ -431,6 +522,9 @@ __global__ __launch_bounds__(A6_THREADS, 2) void kf_attn64_dkv_kernel(
   const int wave_kv_min = kt * A6_BT + w * 32;
   const int kvrow_g = wave_kv_min + l31;
   const float scale2 = scale * KF_LOG2E;
+  // VARLEN is non-causal; the length bounds the q axis as well as the kv axis
+  const int causal = VARLEN ? 0 : causal_arg;
+  const int kv_len = kf_len(len_arg, b, S);
   unsigned short* dkp = dk + ((b * S + kvrow_g) * (int64_t)Hkv + hkv) * A6_D;
   unsigned short* dvp = dv + ((b * S + kvrow_g) * (int64_t)Hkv + hkv) * A6_D;
 
@@ -457,7 +551,11 @@ __global__ __launch_bounds__(A6_THREADS, 2) void kf_attn64_dkv_kernel(
   }
 
   const int qt0 = causal ? (kt * A6_BT) / A6_TT : 0;
-  const int per_head = S / A6_TT - qt0;
+  // VARLEN: q tiles wholly past the length are not visited; q rows >= the
+  // length inside the last tile carry lse = +inf, so P and dS are exactly 0
+  // for them with no mask on the q axis
+  const int per_head =
+      (VARLEN ? (kv_len + A6_TT - 1) / A6_TT : S / A6_TT) - qt0;
   const int total = g * per_head;
 
   kf_stage64 qs, ds;
@@ -578,7 +676,7 @@ KF_EXPORT int kf_attn64_fwd(void* o, float* lse, const void* q, const void* k,
   if (qts == 0) qts = Hq * A6_D;
   if (kts == 0) kts = Hkv * A6_D;
   dim3 grid((unsigned)(S / A6_BT), (unsigned)Hq, (unsigned)B);
-  hipLaunchKernelGGL(kf_attn64_fwd_kernel, grid, dim3(A6_THREADS), 0,
+  hipLaunchKernelGGL(kf_attn64_fwd_kernel<false>, grid, dim3(A6_THREADS), 0,
                      (hipStream_t)stream, (unsigned short*)o, lse,
                      (const unsigned short*)q, (const unsigned short*)k,
                      (const unsigned short*)v, (int)S, (int)Hq, (int)Hkv, qts,
@@ -607,7 +705,7 @@ KF_EXPORT int kf_attn64_bwd(void* dq, void* dk, void* dv, const void* dout,
   int err = (int)hipGetLastError();
   if (err) return err;
   dim3 gq((unsigned)(S / A6_BT), (unsigned)Hq, (unsigned)B);
-  hipLaunchKernelGGL(kf_attn64_dq_kernel, gq, dim3(A6_THREADS), 0,
+  hipLaunchKernelGGL(kf_attn64_dq_kernel<false>, gq, dim3(A6_THREADS), 0,
                      (hipStream_t)stream, (unsigned short*)dq,
                      (const unsigned short*)q, (const unsigned short*)k,
                      (const unsigned short*)v, (const unsigned short*)dout,
@@ -616,12 +714,76 @@ KF_EXPORT int kf_attn64_bwd(void* dq, void* dk, void* dv, const void* dout,
   err = (int)hipGetLastError();
   if (err) return err;
   dim3 gkv((unsigned)(S / A6_BT), (unsigned)Hkv, (unsigned)B);
-  hipLaunchKernelGGL(kf_attn64_dkv_kernel, gkv, dim3(A6_THREADS), 0,
+  hipLaunchKernelGGL(kf_attn64_dkv_kernel<false>, gkv, dim3(A6_THREADS), 0,
                      (hipStream_t)stream, (unsigned short*)dk,
                      (unsigned short*)dv, (const unsigned short*)q,
                      (const unsigned short*)k, (const unsigned short*)v,
                      (const unsigned short*)dout, lse, (const float*)delta,
                      (int)S, (int)Hq, (int)Hkv, qts, kts, scale, causal,
                      (int)kv_len);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------ per-sequence lengths (VARLEN) --
+// seq_lens: device int32 [B]. Non-causal. Same three backward launches; o and
+// lse must come from kf_attn64_fwd_varlen with the same seq_lens.
+KF_EXPORT int kf_attn64_fwd_varlen(void* o, float* lse, const void* q,
+                                   const void* k, const void* v,
+                                   const int32_t* seq_lens, int64_t B,
+                                   int64_t S, int64_t Hq, int64_t Hkv,
+                                   int64_t qts, int64_t kts, float scale,
+                                   void* stream) {
+  if (!seq_lens || kf_attn64_args_bad(B, S, Hq, Hkv, 0, S))
+    return (int)hipErrorInvalidValue;
+  if (qts == 0) qts = Hq * A6_D;
+  if (kts == 0) kts = Hkv * A6_D;
+  dim3 grid((unsigned)(S / A6_BT), (unsigned)Hq, (unsigned)B);
+  hipLaunchKernelGGL(kf_attn64_fwd_kernel<true>, grid, dim3(A6_THREADS), 0,
+                     (hipStream_t)stream, (unsigned short*)o, lse,
+                     (const unsigned short*)q, (const unsigned short*)k,
+                     (const unsigned short*)v, (int)S, (int)Hq, (int)Hkv, qts,
+                     kts, scale, 0, (const int*)seq_lens);
+  return (int)hipGetLastError();
+}
+
+KF_EXPORT int kf_attn64_bwd_varlen(void* dq, void* dk, void* dv,
+                                   const void* dout, const void* q,
+                                   const void* k, const void* v, const void* o,
+                                   const float* lse, float* delta,
+                                   const int32_t* seq_lens, int64_t B,
+                                   int64_t S, int64_t Hq, int64_t Hkv,
+                                   int64_t qts, int64_t kts, float scale,
+                                   void* stream) {
+  if (!seq_lens || kf_attn64_args_bad(B, S, Hq, Hkv, 0, S))
+    return (int)hipErrorInvalidValue;
+  if (qts == 0) qts = Hq * A6_D;
+  if (kts == 0) kts = Hkv * A6_D;
+  const int64_t rows = B * S * Hq;
+  const int64_t dblocks = (rows + A6_THREADS / 8 - 1) / (A6_THREADS / 8);
+  if (dblocks > 0x7fffffff) return (int)hipErrorInvalidValue;
+  // padded rows have o = 0, hence delta = 0: the delta pass is unchanged
+  hipLaunchKernelGGL(kf_attn64_delta_kernel, dim3((unsigned)dblocks),
+                     dim3(A6_THREADS), 0, (hipStream_t)stream, delta,
+                     (const unsigned short*)o, (const unsigned short*)dout,
+                     rows, (int)S, (int)Hq);
+  int err = (int)hipGetLastError();
+  if (err) return err;
+  dim3 gq((unsigned)(S / A6_BT), (unsigned)Hq, (unsigned)B);
+  hipLaunchKernelGGL(kf_attn64_dq_kernel<true>, gq, dim3(A6_THREADS), 0,
+                     (hipStream_t)stream, (unsigned short*)dq,
+                     (const unsigned short*)q, (const unsigned short*)k,
+                     (const unsigned short*)v, (const unsigned short*)dout,
+                     lse, (const float*)delta, (int)S, (int)Hq, (int)Hkv, qts,
+                     kts, scale, 0, (const int*)seq_lens);
+  err = (int)hipGetLastError();
+  if (err) return err;
+  dim3 gkv((unsigned)(S / A6_BT), (unsigned)Hkv, (unsigned)B);
+  hipLaunchKernelGGL(kf_attn64_dkv_kernel<true>, gkv, dim3(A6_THREADS), 0,
+                     (hipStream_t)stream, (unsigned short*)dk,
+                     (unsigned short*)dv, (const unsigned short*)q,
+                     (const unsigned short*)k, (const unsigned short*)v,
+                     (const unsigned short*)dout, lse, (const float*)delta,
+                     (int)S, (int)Hq, (int)Hkv, qts, kts, scale, 0,
+                     (const int*)seq_lens);
   return (int)hipGetLastError();
 }

@@ -159,6 +159,16 @@ KF_EXPORT int kf_attn64_bwd(void* dq, void* dk, void* dv, const void* dout,
     const float* lse, float* delta, int64_t B, int64_t S, int64_t Hq,
     int64_t Hkv, int64_t qts, int64_t kts, float scale, int causal,
     int64_t kv_len, void* stream);
+// per-sequence lengths: seq_lens device int32 [B], non-causal
+KF_EXPORT int kf_attn64_fwd_varlen(void* o, float* lse, const void* q,
+    const void* k, const void* v, const int32_t* seq_lens, int64_t B,
+    int64_t S, int64_t Hq, int64_t Hkv, int64_t qts, int64_t kts, float scale,
+    void* stream);
+KF_EXPORT int kf_attn64_bwd_varlen(void* dq, void* dk, void* dv,
+    const void* dout, const void* q, const void* k, const void* v,
+    const void* o, const float* lse, float* delta, const int32_t* seq_lens,
+    int64_t B, int64_t S, int64_t Hq, int64_t Hkv, int64_t qts, int64_t kts,
+    float scale, void* stream);
 
 // ---- decode attention over the KV cache (attention_decode.hip) ----
 KF_EXPORT int kf_attn_decode(void* out, void* part_o, void* part_ml,

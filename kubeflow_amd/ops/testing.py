@@ -32,7 +32,8 @@ from . import reference as R
 
 __all__ = [
     "row_err", "col_err", "rel_err", "attention_inputs", "attention_oracle",
-    "emulated", "attention_case", "AttnCase", "rope_oracle",
+    "emulated", "attention_case", "attention_case_varlen", "AttnCase",
+    "rope_oracle",
     "rms_norm_oracle", "layer_norm_oracle", "swiglu_oracle",
     "cross_entropy_oracle", "adamw_oracle", "decode_oracle",
     "linear_residual_oracle",
@@ -234,6 +235,49 @@ def attention_case(B: int, S: int, Hq: int, Hkv: int, causal: bool,
                   else torch.tensor(positions))
     oracle = dict(zip(_OUTS, attention_oracle(*inputs, causal, **kw)))
     emu = dict(zip(_OUTS, emulated(*inputs, causal, **kw)))
+    emu_err = {n: row_err(emu[n], oracle[n]) for n in ("o", "dq", "dk", "dv")}
+    bound = {n: ROW_BOUND_FACTOR * e for n, e in emu_err.items()}
+    _ATTN_CACHE[key] = AttnCase(inputs, oracle, emu_err, bound)
+    return _ATTN_CACHE[key]
+
+
+def _embed_varlen(fn, inputs, seq_lens):
+    """Run fn (attention_oracle / emulated, non-causal) on each sequence's
+    [b:b+1, :L] slices and embed (o, lse, dq, dk, dv) into zero tensors of
+    the full shape: rows past a length are zero in every output."""
+    q, k, v, dout = inputs
+    B, S, Hq, D = q.shape
+    Hkv = k.shape[2]
+    out = {"o": torch.zeros(B, S, Hq, D), "lse": torch.zeros(B, Hq, S),
+           "dq": torch.zeros(B, S, Hq, D), "dk": torch.zeros(B, S, Hkv, D),
+           "dv": torch.zeros(B, S, Hkv, D)}
+    for b, L in enumerate(seq_lens):
+        o, lse, dq, dk, dv = fn(q[b:b + 1, :L], k[b:b + 1, :L],
+                                v[b:b + 1, :L], dout[b:b + 1, :L], False)
+        out["o"][b, :L], out["lse"][b, :, :L] = o[0], lse[0]
+        out["dq"][b, :L], out["dk"][b, :L], out["dv"][b, :L] = \
+            dq[0], dk[0], dv[0]
+    return out
+
+
+def attention_case_varlen(B: int, S: int, Hq: int, Hkv: int,
+                          seq_lens: Tuple[int, ...], D: int = 64,
+                          seed: int = 1234) -> AttnCase:
+    """attention_case for a right-padded batch with one length per sequence
+    (non-causal): sequence b attends within its first seq_lens[b] rows, and
+    o, dq, dk, dv are zero past them (lse is left 0 there). Inputs are the
+    plain seeded ones; a test may overwrite k/v rows past a length, which the
+    oracle never reads. emu_err / bound come from row_err over the whole
+    embedded tensors, not per sequence: a length-1 sequence has no emulation
+    error at all and would give a zero bound."""
+    seq_lens = tuple(int(L) for L in seq_lens)
+    assert len(seq_lens) == B and all(1 <= L <= S for L in seq_lens), seq_lens
+    key = ("varlen", B, S, Hq, Hkv, seq_lens, D, seed)
+    if key in _ATTN_CACHE:
+        return _ATTN_CACHE[key]
+    inputs = attention_inputs(B, S, Hq, Hkv, D, seed)
+    oracle = _embed_varlen(attention_oracle, inputs, seq_lens)
+    emu = _embed_varlen(emulated, inputs, seq_lens)
     emu_err = {n: row_err(emu[n], oracle[n]) for n in ("o", "dq", "dk", "dv")}
     bound = {n: ROW_BOUND_FACTOR * e for n, e in emu_err.items()}
     _ATTN_CACHE[key] = AttnCase(inputs, oracle, emu_err, bound)

@@ -109,8 +109,11 @@ class InferenceEngine:
         self.model.eval()
         cfg = self.model.cfg
         # classifier models (BERT family): no KV cache / graphs — each
-        # request is one batched forward; same-length prompts batch, the
-        # rest pad to a 128 multiple with masked_attention(kv_len)
+        # request is one batched forward; prompts whose lengths round up to
+        # the same 128 multiple batch together, padded to it, with one length
+        # per row (flash_attention seq_lens). Head dim 128 on the GPU has no
+        # per-sequence mask: only equal-length prompts batch there, padded
+        # with masked_attention(kv_len)
         self.classify = hasattr(cfg, "n_classes")
         if self.classify:
             self.max_batch = max_batch
@@ -128,7 +131,10 @@ class InferenceEngine:
             self._stop = False
             self._thread = None
             self.stats = {"requests": 0, "completed": 0, "tokens_out": 0,
-                          "prefill_tokens": 0, "graph_replays": 0}
+                          "prefill_tokens": 0, "graph_replays": 0,
+                          "classify_batches": 0}
+            self._classify_varlen = not (self.device.type == "cuda"
+                                         and cfg.head_dim != 64)
             return
         # KF_SERVE_QUANT=fp8: per-output-row OCP e4m3 weight-only quant
         # for the DECODE linears (W8A16 — halves the weight traffic the
@@ -264,15 +270,25 @@ class InferenceEngine:
 
     @torch.no_grad()
     def _classify_batch(self) -> int:
-        """Drain up to max_batch same-length classify requests and run
-        one padded forward (masked_attention over the real length)."""
+        """Drain up to max_batch classify requests of one length bucket and
+        run one padded forward. A bucket is the prompt length rounded up to a
+        128 multiple (the first taken request sets it), so under 128 GEMM
+        rows per request are padding; the rows are padded to the bucket and
+        attention gets one length per row (seq_lens). With head dim 128 on
+        the GPU a bucket is one exact length (scalar kv_len mask). Requests
+        of other buckets go back on the queue. stats["classify_batches"]
+        counts the forwards."""
+        def bucket(r):
+            n = len(r.prompt)
+            return (n + 127) // 128 * 128 if self._classify_varlen else n
+
         taken, back = [], []
         while len(taken) < self.max_batch:
             try:
                 r = self.pending.get_nowait()
             except queue.Empty:
                 break
-            if not taken or len(r.prompt) == len(taken[0].prompt):
+            if not taken or bucket(r) == bucket(taken[0]):
                 taken.append(r)
             else:
                 back.append(r)
@@ -281,13 +297,18 @@ class InferenceEngine:
         if not taken:
             return 0
         try:
-            S = len(taken[0].prompt)
+            lens = [len(r.prompt) for r in taken]
+            S = max(lens)
             Sp = (S + 127) // 128 * 128
-            toks = torch.zeros(len(taken), Sp, dtype=torch.int64,
-                               device=self.device)
+            toks = torch.zeros(len(taken), Sp, dtype=torch.int64)
             for i, r in enumerate(taken):
-                toks[i, :S] = torch.tensor(r.prompt, dtype=torch.int64)
-            logits = self.model(toks, kv_len=S if Sp > S else None)
+                toks[i, :lens[i]] = torch.tensor(r.prompt, dtype=torch.int64)
+            toks = toks.to(self.device)
+            self.stats["classify_batches"] += 1
+            if min(lens) == S:  # equal lengths: the scalar mask (or none)
+                logits = self.model(toks, kv_len=S if Sp > S else None)
+            else:
+                logits = self.model(toks, seq_lens=lens)
             probs = torch.softmax(logits.float(), dim=-1).cpu()
             now = time.time()
             for i, r in enumerate(taken):

@@ -150,7 +150,14 @@ def synthetic_batch(spec: dict, cfg, device, rank: int, step: int):
         B = int(spec.get("micro_batch", 32))
         S = int(spec.get("seq_len", 128))
         V = cfg.vocab_size
-        x = torch.randint(0, V, (B, S), generator=g)
+        if spec.get("var_len"):
+            # right-padded rows: lengths in [1, S], tokens from [1, V), id 0
+            # (the job's pad_token_id) fills the tail
+            lens = torch.randint(1, S + 1, (B,), generator=g)
+            x = torch.randint(1, V, (B, S), generator=g)
+            x = x.masked_fill(torch.arange(S)[None, :] >= lens[:, None], 0)
+        else:
+            x = torch.randint(0, V, (B, S), generator=g)
         y = torch.randint(0, cfg.n_classes, (B,), generator=g)
         return x.to(device), y.to(device)
     # mnist-style dense input
@@ -307,6 +314,8 @@ def main(argv=None):
         if ep_ctx is not None:
             ep_ctx.sync_replicated(model)
         cfg = getattr(model, "cfg", None)
+        if spec.get("var_len") and hasattr(cfg, "pad_token_id"):
+            cfg.pad_token_id = 0  # synthetic_batch pads classify rows with 0
         tcfg = TrainConfig(
             lr=float(spec.get("lr", 3e-4)),
             weight_decay=float(spec.get("weight_decay", 0.1)),
