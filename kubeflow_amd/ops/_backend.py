@@ -103,14 +103,13 @@ SIGNATURES: dict[str, list] = {
     "kf_grad_sumsq": [_FP, _FP, _P, _I64, _P],
     "kf_ce_fwd": [_FP, _FP, _P, _PI64, _I64, _I64, _I64, _P],
     "kf_ce_bwd": [_P, _P, _FP, _PI64, _FP, _I64, _I64, _I64, _P],
-    "kf_skinny_gemm": [_P, _P, _P, _P, _FP, _F] + [_I64] * 7 + [_P],
-    "kf_skinny_gemm_q8": [_P, _P, _P, _FP, _P, _FP, _F] + [_I64] * 7 + [_P],
+    "kf_skinny_gemm": [_P, _P, _P, _P] + [_I64] * 6 + [_P],
+    "kf_skinny_gemm_q8": [_P, _P, _P, _FP, _P] + [_I64] * 6 + [_P],
     "kf_kv_store": [_P] * 6 + [_I64, _I64, _I64, _P],
     "kf_decode_rope_store": [_P, _P, _P, _P, _FP, _FP, _PI32, _P] +
                             [_I64] * 5 + [_P],
     "kf_attn_fwd": _ATTN_FWD,
     "kf_attn_fwd4": _ATTN_FWD,
-    "kf_attn_fwd5": _ATTN_FWD,
     # ..., B, Sq, Skv, Hq, Hkv, D, qts, kts, scale, qoff, stream
     "kf_attn_fwd4_rect": [_P, _FP, _P, _P, _P] + [_I64] * 8 + [_F, _I64, _P],
     # scripts/attn_ablate.py, scripts/probe_tr16.py

@@ -340,17 +340,6 @@ __global__ __launch_bounds__(256) void kf_attn_dkv_kernel(
   }
 }
 
-// dK/dV pass on the 8-wave path: KF_ATTN_BWD_IMPL=1 selects the split
-// dv8 + dk8 pair (bisection), anything else the fused kf_attn_dkv8f kernel.
-static int kf_attn_bwd_impl() {
-  static int cached = -1;
-  if (cached < 0) {
-    const char* e = getenv("KF_ATTN_BWD_IMPL");
-    cached = (e && e[0] == '1') ? 1 : 2;
-  }
-  return cached;
-}
-
 KF_EXPORT int kf_attn_bwd(void* dq, void* dk, void* dv, const void* dout,
                           const void* q, const void* k, const void* v,
                           const void* o, const float* lse, float* delta,
@@ -395,10 +384,6 @@ KF_EXPORT int kf_attn_bwd_rope(void* dq, void* dk, void* dv, const void* dout,
                                qts, kts, dqts, scale, causal, cost, sint,
                                pos_offset, stream);
     if (err) return err;
-    if (kf_attn_bwd_impl() == 1)
-      return kf_attn_bwd8_dkv_rope(dk, dv, q, k, v, dout, lse, delta, B, S,
-                                   Hq, Hkv, qts, kts, dkts, scale, causal,
-                                   cost, sint, pos_offset, stream);
     return kf_attn_bwd8_dkv_fused_rope(dk, dv, q, k, v, dout, lse, delta, B,
                                        S, Hq, Hkv, qts, kts, dkts, scale,
                                        causal, cost, sint, pos_offset,

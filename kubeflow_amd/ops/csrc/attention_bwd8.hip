@@ -39,8 +39,9 @@
 // staging offsets (255 VGPRs, scratch 0; details at the kernel).
 // Measured on MI355X, B7 S4096 Hq32 Hkv8 causal: dv8 + dk8 3.21 ms, dkv8f
 // 2.26 ms per call, bit-identical dK/dV; llama3-8b train step 1368.6 ->
-// 1334.9 ms (profiles/r03_attn_bwd_fused.md). The split pair stays for
-// bisection (KF_ATTN_BWD_IMPL=1).
+// 1334.9 ms (profiles/r03_attn_bwd_fused.md). The split pair stays as the
+// bit-exact reference the tests hold dkv8f to (kf_attn_bwd8_dkv[_rope]);
+// kf_attn_bwd never launches it.
 //
 // The dq8, dk8 and dkv8f store epilogues optionally apply the RoPE adjoint
 // (cost/sint != nullptr): acc[dt] and acc[dt+2] hold the rotate-half pair
@@ -243,7 +244,7 @@ __global__ __launch_bounds__(512, 2) void kf_attn_dq8_kernel(
 }
 
 // --------------------------------------------------------------- pass dKV --
-// Split dV and dK kernels (KF_ATTN_BWD_IMPL=1; the default is the fused
+// Split dV and dK kernels (the test reference; kf_attn_bwd runs the fused
 // kf_attn_dkv8f below): carrying both 64-register accumulators in one
 // kernel spilled 62 VGPRs at the 2-waves/SIMD budget, and recomputing S in
 // a second kernel (+25% MFMA) was far cheaper than scratch traffic.

@@ -19,7 +19,7 @@
 // spanning one row. Next-tile global loads are issued before the compute of
 // the current tile and written to LDS after it (register prefetch).
 //
-// Math is the swapped form of kf_attn_fwd8: S^T = mfma(K, Q) puts one q row
+// Math is the swapped form of kf_attn_fwd4: S^T = mfma(K, Q) puts one q row
 // in each lane's accumulator column, so the online-softmax max/sum are
 // register reductions plus one shfl_xor(32); P^T/dS^T turn into MFMA
 // B-fragments in registers (cvt_pk + permlane32_swap: kf_exchange, derived

@@ -1,16 +1,16 @@
 // attention_fwd4.hip — v4 causal flash-attention forward (bf16, GQA, gfx950).
 //
-// Round-2 rework of the 8-wave swapped-QK^T kernel (attention_fwd.hip v3,
-// 296 TF causal) applying the CDNA4 guide's full verified technique stack
+// Round-2 rework of the round-1 8-wave swapped-QK^T kernel (296 TF causal,
+// since removed; docs/ROUND1.md has its ladder) applying the CDNA4 guide's full verified technique stack
 // (§B 8-warp ladder, §5.5 T3/T10/T13/T14) plus a VALU-overlap pipeline:
 //  * KVBLK=64 K/V tiles DOUBLE-BUFFERED in LDS (64 KiB total), with the
 //    async-STAGE split: next tile's global loads issue at the top of the
 //    iteration and land during compute; LDS writes + one barrier per tile
 //    (T3 minimum 2-phase recipe + T14) — replaces the serial
-//    sync/load/scatter/sync staging of v3.
+//    sync/load/scatter/sync staging of the round-1 kernel.
 //  * V is stored in a [d/16-slab][kv/4-tile][4][16] subtiled layout and the
 //    PV A-operand (V^T) is read with ds_read_b64_tr_b16, the gfx950
-//    hardware transpose read (T10) — replaces v3's 8-scalar-ds_write
+//    hardware transpose read (T10) — replaces an 8-scalar-ds_write
 //    transpose-scatter per staged vector. Lane mapping HW-verified by
 //    scripts/probe_tr16.py (each lane reads 8 B at its own address; each
 //    4-lane subgroup supplies one 16-elem tile row; lane gets column l&15).
@@ -23,7 +23,7 @@
 //    branch); fully-masked sub-blocks are skipped per wave.
 //  * swapped QK^T (S^T = mfma(K, Q)) with fully in-register softmax and
 //    cvt_pk_bf16 + permlane32_swap P repack, K XOR-swizzled LDS, setprio
-//    around MFMA clusters — carried over from v3.
+//    around MFMA clusters — carried over from round 1.
 //
 // Layout: bshd q [B,S,Hq,D], k/v [B,S,Hkv,D], o [B,S,Hq,D], lse [B,Hq,S]
 // fp32. D == 128, S % 256 == 0 (wrapper pads). Reference behavior anchor:

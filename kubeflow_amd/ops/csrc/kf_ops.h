@@ -69,13 +69,11 @@ KF_EXPORT int kf_ce_bwd(void* dlogits, const void* logits, const float* lse,
 
 // ---- skinny_gemm.hip / kv_store.hip / decode_fused.hip ----
 KF_EXPORT int kf_skinny_gemm(void* c, const void* a, const void* w,
-    const void* res, const float* rmsg, float rms_eps, int64_t swiglu,
-    int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldc,
-    void* stream);
+    const void* res, int64_t M, int64_t N, int64_t K, int64_t lda,
+    int64_t ldw, int64_t ldc, void* stream);
 KF_EXPORT int kf_skinny_gemm_q8(void* c, const void* a, const void* w8,
-    const float* wscale, const void* res, const float* rmsg, float rms_eps,
-    int64_t swiglu, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
-    int64_t ldc, void* stream);
+    const float* wscale, const void* res, int64_t M, int64_t N, int64_t K,
+    int64_t lda, int64_t ldw, int64_t ldc, void* stream);
 KF_EXPORT int kf_kv_store(void* ck, void* cv, const void* k, const void* v,
     const void* slots, const void* positions, int64_t smax, int64_t row,
     int64_t n, void* stream);
@@ -84,16 +82,13 @@ KF_EXPORT int kf_decode_rope_store(void* qout, void* ck, void* cv,
     const void* positions, int64_t N, int64_t Hq, int64_t Hkv, int64_t D,
     int64_t smax, void* stream);
 
-// ---- attention forward, D = 128 (attention_fwd.hip, _fwd4.hip, _fwd5.hip) --
-// kf_attn_fwd dispatches on KF_ATTN_IMPL: 4 (default) -> kf_attn_fwd4,
-// 5 -> kf_attn_fwd5, 3 -> the 8-wave v3 kernel in attention_fwd.hip.
+// ---- attention forward, D = 128 (attention_fwd.hip, attention_fwd4.hip) ----
+// kf_attn_fwd dispatches on S: S % 256 == 0 -> kf_attn_fwd4, any other
+// multiple of 128 -> the 4-wave kernel in attention_fwd.hip.
 KF_EXPORT int kf_attn_fwd(void* o, float* lse, const void* q, const void* k,
     const void* v, int64_t B, int64_t S, int64_t Hq, int64_t Hkv, int64_t D,
     int64_t qts, int64_t kts, float scale, int causal, void* stream);
 KF_EXPORT int kf_attn_fwd4(void* o, float* lse, const void* q, const void* k,
-    const void* v, int64_t B, int64_t S, int64_t Hq, int64_t Hkv, int64_t D,
-    int64_t qts, int64_t kts, float scale, int causal, void* stream);
-KF_EXPORT int kf_attn_fwd5(void* o, float* lse, const void* q, const void* k,
     const void* v, int64_t B, int64_t S, int64_t Hq, int64_t Hkv, int64_t D,
     int64_t qts, int64_t kts, float scale, int causal, void* stream);
 KF_EXPORT int kf_attn_fwd4_rect(void* o, float* lse, const void* q,

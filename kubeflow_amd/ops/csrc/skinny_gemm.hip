@@ -18,66 +18,6 @@
 typedef __bf16 kf_bf16x8s __attribute__((ext_vector_type(8)));
 typedef float kf_f32x4s __attribute__((ext_vector_type(4)));
 
-// Fused-RMSNorm support: when rmsg != null, A rows are normalized
-// in-flight — the block computes each A row's rstd once (it reads the
-// whole row over the chunk loop anyway; A is LLC-hot) and scales
-// fragments by rstd[row] * gamma[k]. Removes the two standalone rmsnorm
-// launches per decode layer (profiles/r02_decode_anatomy.md).
-typedef unsigned short kf_u16x8q __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float kf_row_rstd(const unsigned short* row,
-                                             int64_t K, float eps) {
-  // all 64 lanes of the calling wave stride one row cooperatively
-  float acc = 0.f;
-  const int lane = threadIdx.x & (KF_WAVE - 1);
-  for (int64_t i = (int64_t)lane * 8; i < K; i += KF_WAVE * 8) {
-    const kf_u16x8q x = *reinterpret_cast<const kf_u16x8q*>(row + i);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float f = kf_bf16_to_f32(x[j]);
-      acc += f * f;
-    }
-  }
-  for (int off = 32; off; off >>= 1) acc += __shfl_xor(acc, off, KF_WAVE);
-  return rsqrtf(acc / (float)K + eps);
-}
-
-// Fused-SwiGLU support (the w2 projection): when swiglu != 0, A is the
-// RAW w13 output [M, 2K] (gate rows [0,K), up rows [K,2K)) and fragments
-// are silu(gate)*up computed in-flight — removes the standalone swiglu
-// kernel + the y round-trip from the decode layer. Pure elementwise on
-// the A side (no extra row pass, unlike the rms fusion which measured
-// negative).
-__device__ __forceinline__ kf_bf16x8s kf_swiglu8(kf_bf16x8s g,
-                                                 kf_bf16x8s u) {
-  union {
-    kf_bf16x8s v;
-    unsigned short us[8];
-  } gi, ui, o;
-  gi.v = g;
-  ui.v = u;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float gf = kf_bf16_to_f32(gi.us[j]);
-    const float uf = kf_bf16_to_f32(ui.us[j]);
-    o.us[j] = kf_f32_to_bf16(gf / (1.f + __expf(-gf)) * uf);
-  }
-  return o.v;
-}
-
-__device__ __forceinline__ kf_bf16x8s kf_rms_scale8(
-    kf_bf16x8s a, float rstd, const float* __restrict__ g) {
-  union {
-    kf_bf16x8s v;
-    unsigned short u[8];
-  } in, out;
-  in.v = a;
-#pragma unroll
-  for (int j = 0; j < 8; ++j)
-    out.u[j] = kf_f32_to_bf16(kf_bf16_to_f32(in.u[j]) * rstd * g[j]);
-  return out.v;
-}
-
 #define SK_NT 16      // N columns per block
 // K-split ways (waves/block) is a template knob: small-N shapes (wo:
 // N=4096 -> 256 blocks == 1 block/CU == 1 wave/SIMD at 4 waves) are
@@ -167,16 +107,14 @@ __global__ __launch_bounds__(SKW * 64, 2) void kf_skinny_gemm_kernel(
 // MT = M-tile (16 or 32 batch rows); W traffic is identical, the wider
 // tile just adds a second A fragment + accumulator (decode buckets > 16
 // otherwise fell back to hipBLASLt).
-template <int MT, bool SWIGLU>
+template <int MT>
 __global__ __launch_bounds__(SKL_W * 64, 2) void kf_skinny_lds_kernel(
     unsigned short* __restrict__ c, const unsigned short* __restrict__ a,
     const unsigned short* __restrict__ w,
     const unsigned short* __restrict__ res,
-    const float* __restrict__ rmsg, float rms_eps, int M,
-    int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldc) {
+    int M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldc) {
   __shared__ unsigned short wbuf[2][SK_NT][SKL_STRIDE];
   __shared__ float red[SKL_W][MT][SK_NT];
-  __shared__ float rstd_lds[MT];
 
   const int64_t n0 = (int64_t)blockIdx.x * SK_NT;
   const int tid = threadIdx.x;
@@ -196,17 +134,6 @@ __global__ __launch_bounds__(SKL_W * 64, 2) void kf_skinny_lds_kernel(
     arow[t] = a + (arow_ok[t] ? l15 + 16 * t : 0) * lda;
   }
   const kf_bf16x8s zero8 = kf_bf16x8s{0, 0, 0, 0, 0, 0, 0, 0};
-  float rstd[NMT];
-  if (rmsg) {
-    // wave wv computes rstd for rows {wv*MT/8 .. } (MT/8 rows per wave)
-    for (int r = wv * (MT / SKL_W); r < (wv + 1) * (MT / SKL_W); ++r) {
-      const float v = kf_row_rstd(a + (r < M ? r : 0) * lda, K, rms_eps);
-      if (lane == 0) rstd_lds[r] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < NMT; ++t) rstd[t] = rstd_lds[l15 + 16 * t];
-  }
   // writer: wave wv stages rows {2wv, 2wv+1}, lane covers elems
   // [lane*8, lane*8+8) of each 512-elem row slice
   const unsigned short* wr0 = w + (n0 + 2 * wv) * ldw + lane * 8;
@@ -217,21 +144,12 @@ __global__ __launch_bounds__(SKL_W * 64, 2) void kf_skinny_lds_kernel(
   kf_bf16x8s st0 = *reinterpret_cast<const kf_bf16x8s*>(wr0);
   kf_bf16x8s st1 = *reinterpret_cast<const kf_bf16x8s*>(wr1);
   kf_bf16x8s af0[NMT], af1[NMT];
-  kf_bf16x8s uf0[SWIGLU ? NMT : 1], uf1[SWIGLU ? NMT : 1];
 #pragma unroll
   for (int t = 0; t < NMT; ++t) {
     af0[t] = arow_ok[t]
         ? *reinterpret_cast<const kf_bf16x8s*>(arow[t] + ke0) : zero8;
     af1[t] = arow_ok[t]
         ? *reinterpret_cast<const kf_bf16x8s*>(arow[t] + ke0 + 32) : zero8;
-    if constexpr (SWIGLU) {
-      uf0[t] = arow_ok[t]
-          ? *reinterpret_cast<const kf_bf16x8s*>(arow[t] + K + ke0)
-          : zero8;
-      uf1[t] = arow_ok[t]
-          ? *reinterpret_cast<const kf_bf16x8s*>(arow[t] + K + ke0 + 32)
-          : zero8;
-    }
   }
   *reinterpret_cast<kf_bf16x8s*>(&wbuf[0][2 * wv][lane * 8]) = st0;
   *reinterpret_cast<kf_bf16x8s*>(&wbuf[0][2 * wv + 1][lane * 8]) = st1;
@@ -239,13 +157,8 @@ __global__ __launch_bounds__(SKL_W * 64, 2) void kf_skinny_lds_kernel(
     kf_bf16x8s a0[NMT], a1[NMT];
 #pragma unroll
     for (int t = 0; t < NMT; ++t) {
-      if constexpr (SWIGLU) {
-        a0[t] = kf_swiglu8(af0[t], uf0[t]);
-        a1[t] = kf_swiglu8(af1[t], uf1[t]);
-      } else {
-        a0[t] = af0[t];
-        a1[t] = af1[t];
-      }
+      a0[t] = af0[t];
+      a1[t] = af1[t];
     }
     if (ch + 1 < nch) {
       st0 = *reinterpret_cast<const kf_bf16x8s*>(wr0 + (ch + 1) * SKL_KC);
@@ -257,12 +170,6 @@ __global__ __launch_bounds__(SKL_W * 64, 2) void kf_skinny_lds_kernel(
               arow[t] + (ch + 1) * SKL_KC + ke0);
           af1[t] = *reinterpret_cast<const kf_bf16x8s*>(
               arow[t] + (ch + 1) * SKL_KC + ke0 + 32);
-          if constexpr (SWIGLU) {
-            uf0[t] = *reinterpret_cast<const kf_bf16x8s*>(
-                arow[t] + K + (ch + 1) * SKL_KC + ke0);
-            uf1[t] = *reinterpret_cast<const kf_bf16x8s*>(
-                arow[t] + K + (ch + 1) * SKL_KC + ke0 + 32);
-          }
         }
     }
     // one barrier per chunk: makes buffer ch&1's writes visible AND
@@ -272,14 +179,6 @@ __global__ __launch_bounds__(SKL_W * 64, 2) void kf_skinny_lds_kernel(
         *reinterpret_cast<const kf_bf16x8s*>(&wbuf[ch & 1][l15][ke0]);
     kf_bf16x8s wf1 =
         *reinterpret_cast<const kf_bf16x8s*>(&wbuf[ch & 1][l15][ke0 + 32]);
-    if (rmsg) {
-      const float* g0 = rmsg + ch * SKL_KC + ke0;
-#pragma unroll
-      for (int t = 0; t < NMT; ++t) {
-        a0[t] = kf_rms_scale8(a0[t], rstd[t], g0);
-        a1[t] = kf_rms_scale8(a1[t], rstd[t], g0 + 32);
-      }
-    }
 #pragma unroll
     for (int t = 0; t < NMT; ++t) {
       acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0[t], wf0, acc[t],
@@ -350,16 +249,14 @@ __device__ __forceinline__ kf_bf16x8s kf_fp8x8_to_bf16x8(
   return out.v;
 }
 
-template <int MT, bool SWIGLU>
+template <int MT>
 __global__ __launch_bounds__(SKL_W * 64, 2) void kf_skinny_q8_kernel(
     unsigned short* __restrict__ c, const unsigned short* __restrict__ a,
     const unsigned char* __restrict__ w8, const float* __restrict__ wscale,
     const unsigned short* __restrict__ res,
-    const float* __restrict__ rmsg, float rms_eps, int M,
-    int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldc) {
+    int M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldc) {
   __shared__ unsigned char wbuf8[2][SK_NT][SKQ_STRIDE];
   __shared__ float red[SKL_W][MT][SK_NT];
-  __shared__ float rstd_lds[MT];
 
   const int64_t n0 = (int64_t)blockIdx.x * SK_NT;
   const int tid = threadIdx.x;
@@ -379,16 +276,6 @@ __global__ __launch_bounds__(SKL_W * 64, 2) void kf_skinny_q8_kernel(
     arow[t] = a + (arow_ok[t] ? l15 + 16 * t : 0) * lda;
   }
   const kf_bf16x8s zero8 = kf_bf16x8s{0, 0, 0, 0, 0, 0, 0, 0};
-  float rstd[NMT];
-  if (rmsg) {
-    for (int r = wv * (MT / SKL_W); r < (wv + 1) * (MT / SKL_W); ++r) {
-      const float vv = kf_row_rstd(a + (r < M ? r : 0) * lda, K, rms_eps);
-      if (lane == 0) rstd_lds[r] = vv;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < NMT; ++t) rstd[t] = rstd_lds[l15 + 16 * t];
-  }
   // 16 B per lane per row: a full 1 KB (1024 fp8) row slice per wave
   // instruction — same load width as the bf16 kernel, twice the K
   typedef unsigned int kf_u32x4q __attribute__((ext_vector_type(4)));
@@ -400,20 +287,13 @@ __global__ __launch_bounds__(SKL_W * 64, 2) void kf_skinny_q8_kernel(
   kf_u32x4q st0 = *reinterpret_cast<const kf_u32x4q*>(wr0);
   kf_u32x4q st1 = *reinterpret_cast<const kf_u32x4q*>(wr1);
   kf_bf16x8s af[4][NMT];
-  kf_bf16x8s uf[4][SWIGLU ? NMT : 1];
 #pragma unroll
   for (int si = 0; si < 4; ++si)
 #pragma unroll
-    for (int t = 0; t < NMT; ++t) {
+    for (int t = 0; t < NMT; ++t)
       af[si][t] = arow_ok[t]
           ? *reinterpret_cast<const kf_bf16x8s*>(arow[t] + ke0 + 32 * si)
           : zero8;
-      if constexpr (SWIGLU)
-        uf[si][t] = arow_ok[t]
-            ? *reinterpret_cast<const kf_bf16x8s*>(
-                  arow[t] + K + ke0 + 32 * si)
-            : zero8;
-    }
   *reinterpret_cast<kf_u32x4q*>(&wbuf8[0][2 * wv][lane * 16]) = st0;
   *reinterpret_cast<kf_u32x4q*>(&wbuf8[0][2 * wv + 1][lane * 16]) = st1;
   for (int64_t ch = 0; ch < nch; ++ch) {
@@ -421,12 +301,7 @@ __global__ __launch_bounds__(SKL_W * 64, 2) void kf_skinny_q8_kernel(
 #pragma unroll
     for (int si = 0; si < 4; ++si)
 #pragma unroll
-      for (int t = 0; t < NMT; ++t) {
-        if constexpr (SWIGLU)
-          acur[si][t] = kf_swiglu8(af[si][t], uf[si][t]);
-        else
-          acur[si][t] = af[si][t];
-      }
+      for (int t = 0; t < NMT; ++t) acur[si][t] = af[si][t];
     if (ch + 1 < nch) {
       st0 = *reinterpret_cast<const kf_u32x4q*>(wr0 + (ch + 1) * SKQ_KC);
       st1 = *reinterpret_cast<const kf_u32x4q*>(wr1 + (ch + 1) * SKQ_KC);
@@ -434,25 +309,15 @@ __global__ __launch_bounds__(SKL_W * 64, 2) void kf_skinny_q8_kernel(
       for (int si = 0; si < 4; ++si)
 #pragma unroll
         for (int t = 0; t < NMT; ++t)
-          if (arow_ok[t]) {
+          if (arow_ok[t])
             af[si][t] = *reinterpret_cast<const kf_bf16x8s*>(
                 arow[t] + (ch + 1) * SKQ_KC + ke0 + 32 * si);
-            if constexpr (SWIGLU)
-              uf[si][t] = *reinterpret_cast<const kf_bf16x8s*>(
-                  arow[t] + K + (ch + 1) * SKQ_KC + ke0 + 32 * si);
-          }
     }
     __syncthreads();
 #pragma unroll
     for (int si = 0; si < 4; ++si) {
       kf_bf16x8s wf =
           kf_fp8x8_to_bf16x8(&wbuf8[ch & 1][l15][ke0 + 32 * si]);
-      if (rmsg) {
-        const float* g = rmsg + ch * SKQ_KC + ke0 + 32 * si;
-#pragma unroll
-        for (int t = 0; t < NMT; ++t)
-          acur[si][t] = kf_rms_scale8(acur[si][t], rstd[t], g);
-      }
 #pragma unroll
       for (int t = 0; t < NMT; ++t)
         acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(acur[si][t], wf,
@@ -486,10 +351,8 @@ __global__ __launch_bounds__(SKL_W * 64, 2) void kf_skinny_q8_kernel(
 
 KF_EXPORT int kf_skinny_gemm_q8(void* c, const void* a, const void* w8,
                                 const float* wscale, const void* res,
-                                const float* rmsg, float rms_eps,
-                                int64_t swiglu, int64_t M, int64_t N,
-                                int64_t K, int64_t lda, int64_t ldw,
-                                int64_t ldc, void* stream) {
+                                int64_t M, int64_t N, int64_t K, int64_t lda,
+                                int64_t ldw, int64_t ldc, void* stream) {
   if (M < 1 || M > 32 || K % SKQ_KC || N % SK_NT)
     return (int)hipErrorInvalidValue;
   if (lda == 0) lda = K;
@@ -497,54 +360,36 @@ KF_EXPORT int kf_skinny_gemm_q8(void* c, const void* a, const void* w8,
   if (ldc == 0) ldc = N;
   if (ldw % 8 || lda % 8) return (int)hipErrorInvalidValue;
   dim3 grid((unsigned)(N / SK_NT), 1, 1);
-#define KF_SKQ_LAUNCH(MT, SW)                                            \
-  hipLaunchKernelGGL((kf_skinny_q8_kernel<MT, SW>), grid,                \
-                     dim3(SKL_W * 64), 0, (hipStream_t)stream,           \
-                     (unsigned short*)c, (const unsigned short*)a,       \
-                     (const unsigned char*)w8, wscale,                   \
-                     (const unsigned short*)res, rmsg, rms_eps, (int)M,  \
-                     N, K, lda, ldw, ldc)
-  if (M > 16) {
-    if (swiglu) KF_SKQ_LAUNCH(32, true);
-    else KF_SKQ_LAUNCH(32, false);
-  } else {
-    if (swiglu) KF_SKQ_LAUNCH(16, true);
-    else KF_SKQ_LAUNCH(16, false);
-  }
+#define KF_SKQ_LAUNCH(MT)                                                \
+  hipLaunchKernelGGL(kf_skinny_q8_kernel<MT>, grid, dim3(SKL_W * 64), 0, \
+                     (hipStream_t)stream, (unsigned short*)c,            \
+                     (const unsigned short*)a, (const unsigned char*)w8, \
+                     wscale, (const unsigned short*)res, (int)M, N, K,   \
+                     lda, ldw, ldc)
+  if (M > 16) KF_SKQ_LAUNCH(32);
+  else KF_SKQ_LAUNCH(16);
   return (int)hipGetLastError();
 }
 
-// rmsg (nullable, fp32 [K]): fused input RMSNorm — C = res +
-// rmsnorm(A; rmsg, rms_eps) @ W^T (LDS-staged kernels only).
-// swiglu != 0: A is the raw [M, 2K] w13 output; fragments are
-// silu(A[:, :K]) * A[:, K:] computed in-flight (LDS kernels only).
 KF_EXPORT int kf_skinny_gemm(void* c, const void* a, const void* w,
-                             const void* res, const float* rmsg,
-                             float rms_eps, int64_t swiglu, int64_t M,
-                             int64_t N, int64_t K, int64_t lda,
-                             int64_t ldw, int64_t ldc, void* stream) {
+                             const void* res, int64_t M, int64_t N,
+                             int64_t K, int64_t lda, int64_t ldw,
+                             int64_t ldc, void* stream) {
   if (M < 1 || M > 32 || K % 32 || N % SK_NT) return (int)hipErrorInvalidValue;
   if (lda == 0) lda = K;
   if (ldw == 0) ldw = K;
   if (ldc == 0) ldc = N;
   const bool lds_ok = K % SKL_KC == 0 && ldw % 8 == 0 && lda % 8 == 0;
   if (M > 16 && !lds_ok) return (int)hipErrorInvalidValue;
-  if ((rmsg || swiglu) && !lds_ok) return (int)hipErrorInvalidValue;
   dim3 grid((unsigned)(N / SK_NT), 1, 1);
-#define KF_SKL_LAUNCH(MT, SW)                                            \
-  hipLaunchKernelGGL((kf_skinny_lds_kernel<MT, SW>), grid,               \
-                     dim3(SKL_W * 64), 0, (hipStream_t)stream,           \
-                     (unsigned short*)c, (const unsigned short*)a,       \
-                     (const unsigned short*)w,                           \
-                     (const unsigned short*)res, rmsg, rms_eps, (int)M,  \
-                     N, K, lda, ldw, ldc)
-  if (lds_ok && M > 16) {
-    if (swiglu) KF_SKL_LAUNCH(32, true);
-    else KF_SKL_LAUNCH(32, false);
-  } else if (lds_ok) {
-    if (swiglu) KF_SKL_LAUNCH(16, true);
-    else KF_SKL_LAUNCH(16, false);
-  }
+#define KF_SKL_LAUNCH(MT)                                                 \
+  hipLaunchKernelGGL(kf_skinny_lds_kernel<MT>, grid, dim3(SKL_W * 64), 0, \
+                     (hipStream_t)stream, (unsigned short*)c,             \
+                     (const unsigned short*)a, (const unsigned short*)w,  \
+                     (const unsigned short*)res, (int)M, N, K, lda, ldw,  \
+                     ldc)
+  if (lds_ok && M > 16) KF_SKL_LAUNCH(32);
+  else if (lds_ok) KF_SKL_LAUNCH(16);
   // direct-load fallback: 8 waves when the grid can't fill the chip with
   // 4-wave blocks (<2 blocks/CU), 4 otherwise
   else if (N / SK_NT < 512)

@@ -648,13 +648,11 @@ class InferenceEngine:
 
         def _lin(name, wname):
             if qw is not None and name in sel:
-                return lambda li, t, w, rms=None: ops.skinny_linear_q8(
-                    t, *qw[li][wname], rms=rms)
+                return lambda li, t, w: ops.skinny_linear_q8(
+                    t, *qw[li][wname])
             if name in sel:
-                return lambda li, t, w, rms=None: ops.skinny_linear(
-                    t, w, rms=rms)
-            return (lambda li, t, w, rms=None:
-                    F.linear(rms[0](t) if rms else t, w))
+                return lambda li, t, w: ops.skinny_linear(t, w)
+            return lambda li, t, w: F.linear(t, w)
         lin_qkv = _lin("qkv", "wqkv")
         lin_w13 = _lin("w13", "w13")
         if "lm" in sel and qw is not None:
@@ -664,21 +662,20 @@ class InferenceEngine:
         else:
             lin_lm = F.linear
 
-        def _lin_res(name, wname, fuse_swiglu=False):
+        def _lin_res(name, wname):
             if qw is not None and name in sel:
                 return lambda li, t, w, r: ops.skinny_linear_q8(
-                    t, *qw[li][wname], residual=r,
-                    fuse_swiglu=fuse_swiglu)
+                    t, *qw[li][wname], residual=r)
             if name in sel:
                 return lambda li, t, w, r: ops.skinny_linear(
-                    t, w, residual=r, fuse_swiglu=fuse_swiglu)
+                    t, w, residual=r)
             return lambda li, t, w, r: F.linear(t, w) + r
         lin_wo = _lin_res("wo", "wo")
         lin_w2 = _lin_res("w2", "w2")
         x = self.model.embed(tokens)  # [N,1,H]
         cos, sin = self.model.rope_cos, self.model.rope_sin
         for li, layer in enumerate(self.model.layers):
-            # NOTE: fusing the RMSNorms into the GEMM prologue (rms=...)
+            # NOTE: fusing the RMSNorms into the GEMM prologue
             # measured WORSE (replay 4.1 -> 5.8 ms): the per-block rstd
             # pass stalls the weight stream behind 16 LLC row reads per
             # block. Separate norm kernels stay (r02_decode_anatomy.md).
@@ -696,10 +693,10 @@ class InferenceEngine:
                 x = x + layer.moe.decode_dense(layer.mlp_norm(x))
             else:
                 # NOTE: fusing swiglu into the w2 fragment loader
-                # (fuse_swiglu=True) measured WORSE (replay 4.3 -> 5.0,
-                # quant 3.5 -> 4.6): the silu exp chain lands on the
-                # MFMA dependency path and breaks the load pipeline.
-                # The standalone swiglu kernel stays.
+                # measured WORSE (replay 4.3 -> 5.0, quant 3.5 -> 4.6):
+                # the silu exp chain lands on the MFMA dependency path
+                # and breaks the load pipeline. The standalone swiglu
+                # kernel stays (r02_decode_anatomy.md).
                 y = ops.swiglu(lin_w13(li, layer.mlp_norm(x),
                                        layer.w13.weight))
                 x = lin_w2(li, y, layer.w2.weight, x)

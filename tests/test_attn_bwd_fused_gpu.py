@@ -84,8 +84,8 @@ def _plain(name):
     _ok(lib.kf_attn_fwd(_p(o), _fp(lse), _p(q), _p(k), _p(v), B, S, Hq, Hkv,
                         D, 0, 0, scale, int(causal), _stream()), "attn_fwd")
 
-    # new: kf_attn_bwd (routes S % 256 == 0 to the fused dK/dV kernel unless
-    # KF_ATTN_BWD_IMPL=1); it also leaves delta for the per-pass calls
+    # new: kf_attn_bwd (always routes S % 256 == 0 to the fused dK/dV
+    # kernel); it also leaves delta for the per-pass calls
     delta = torch.empty(B, Hq, S, dtype=torch.float32, device=dev)
     new = [torch.full_like(t, float("nan")) for t in (q, k, v)]
     _ok(lib.kf_attn_bwd(_p(new[0]), _p(new[1]), _p(new[2]), _p(dout), _p(q),

@@ -14,15 +14,9 @@ that is never stored fails.
 Branches (kf_attn_fwd / kf_attn_bwd_rope dispatch on S % 256):
   4-wave kf_attn_fwd_kernel + kf_attn_dq_kernel + kf_attn_dkv_kernel for
   S % 256 != 0, with the kf_rope(backward=1) tail when tables are passed;
-  8-wave fwd4 + dq8 + dkv8f for S % 256 == 0, rotation in the epilogues;
-  KF_ATTN_IMPL=3 (fwd8) and 5 (fwd5) forward bisection paths, each in a fresh
-  child process because the switch is cached in a C static.
+  8-wave fwd4 + dq8 + dkv8f for S % 256 == 0, rotation in the epilogues.
 """
 import ctypes
-import json
-import os
-import subprocess
-import sys
 
 import pytest
 import torch
@@ -36,7 +30,6 @@ D = 128
 FWD_BOUND = 2e-2   # test_attention_fwd's bound
 BWD_BOUND = 4e-2   # test_attention_bwd's bound
 LSE_ATOL = 1e-2    # test_attn_d64_gpu.py::test_direct_fwd_lse's bound
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # name -> (B, S, Hq, Hkv, causal)
 PLAIN_CASES = {
@@ -73,8 +66,6 @@ FUSED_CASES = {
     "fused_qkv_s128": (2, 128, 4, 2),    # 4-wave, one q tile
     "fused_qkv_s384": (1, 384, 4, 2),    # 4-wave, three q tiles
 }
-# forward bisection children: (B, S, Hq, Hkv, causal), both S % 256 == 0
-IMPL_CASES = [(1, 512, 4, 2, True), (1, 256, 2, 2, False)]
 
 _cache = {}
 
@@ -269,66 +260,3 @@ def test_fused_qkv_attention_both_metrics(name):
                dv=dv.reshape(B, S, Hkv, D))
     _check(name, got, case)
 
-
-# ------------------------------------------------ forward bisection paths
-
-_CHILD = r"""
-import ctypes, json, sys
-import torch
-from kubeflow_amd.ops import _backend
-from kubeflow_amd.ops import testing as T
-
-lib = _backend.require()
-dev = torch.device("cuda", 0)
-D = 128
-out = {}
-for B, S, Hq, Hkv, causal in json.loads(sys.argv[2]):
-    q, k, v, _ = (t.to(dev) for t in T.attention_inputs(B, S, Hq, Hkv))
-    o = torch.full((B, S, Hq, D), float("nan"), dtype=torch.bfloat16,
-                   device=dev)
-    lse = torch.full((B, Hq, S), float("nan"), dtype=torch.float32,
-                     device=dev)
-    vp = lambda t: ctypes.c_void_p(t.data_ptr())
-    err = lib.kf_attn_fwd(
-        vp(o), ctypes.cast(lse.data_ptr(), ctypes.POINTER(ctypes.c_float)),
-        vp(q), vp(k), vp(v), B, S, Hq, Hkv, D, 0, 0, D ** -0.5, int(causal),
-        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if err:
-        sys.exit(f"kf_attn_fwd failed with hipError_t={err}")
-    torch.cuda.synchronize()
-    out[f"{B}_{S}_{Hq}_{Hkv}_{int(causal)}"] = (o.cpu(), lse.cpu())
-torch.save(out, sys.argv[1])
-"""
-
-
-def _impl_child(impl, tmp_path):
-    """One fresh process with KF_ATTN_IMPL=impl; returns its saved outputs. A
-    nonzero exit status fails here and nothing else is started."""
-    path = str(tmp_path / f"impl{impl}.pt")
-    env = dict(os.environ, KF_ATTN_IMPL=str(impl))
-    env.pop("KF_ATTN_V4", None)
-    r = subprocess.run(
-        [sys.executable, "-c", _CHILD, path, json.dumps(IMPL_CASES)],
-        cwd=REPO, env=env, timeout=120, capture_output=True, text=True)
-    assert r.returncode == 0, (r.returncode, r.stdout[-2000:],
-                               r.stderr[-2000:])
-    return torch.load(path)
-
-
-def _check_impl(impl, tmp_path):
-    saved = _impl_child(impl, tmp_path)
-    for B, S, Hq, Hkv, causal in IMPL_CASES:
-        o, lse = saved[f"{B}_{S}_{Hq}_{Hkv}_{int(causal)}"]
-        case = T.attention_case(B, S, Hq, Hkv, causal)
-        _check(f"impl{impl}_S{S}_{'causal' if causal else 'noncausal'}",
-               dict(o=o, lse=lse), case, outs=("o",))
-
-
-def test_fwd_impl3_child_process(tmp_path):
-    """KF_ATTN_IMPL=3: the round-1 8-wave kf_attn_fwd8_kernel."""
-    _check_impl(3, tmp_path)
-
-
-def test_fwd_impl5_child_process(tmp_path):
-    """KF_ATTN_IMPL=5: kf_attn_fwd5 (4 waves x 64 q rows, parked)."""
-    _check_impl(5, tmp_path)
