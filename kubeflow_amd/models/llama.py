@@ -126,7 +126,12 @@ class MoEMLP(nn.Module):
     """Top-k gated mixture of SwiGLU experts (replaces the dense MLP when
     cfg.n_experts > 0). Expert banks are [E_local, ...] parameter tensors;
     under expert parallelism (parallel/ep.py) each rank owns a contiguous
-    E/N block and tokens travel by all-gather / reduce-scatter."""
+    E/N block and tokens travel by all-gather / reduce-scatter.
+
+    On the GPU (bf16, library loaded, KF_MOE_NATIVE != 0, E <= 64, k <= 8)
+    the routed block is ops.moe_experts: moe.hip routing, dispatch and
+    combine around per-expert library GEMMs, reproducible bit for bit. Every
+    other case runs the per-expert loop in forward()."""
 
     def __init__(self, cfg: LlamaConfig, ep=None):
         super().__init__()
@@ -153,7 +158,18 @@ class MoEMLP(nn.Module):
         if self.ep:
             xf = epmod.all_gather_cat(xf, self.ep)
         # router runs (replicated weights) on whatever token set is local
-        logits = torch.nn.functional.linear(xf, self.gate.weight)
+        logits = self.gate(xf)
+        if (ops.moe_native_ok(xf, cfg.n_experts, cfg.top_k)
+                and logits.dtype == xf.dtype
+                and self.experts_w13.dtype == xf.dtype):
+            # moe.hip: one routing (a single host sync for the split sizes),
+            # one permuted buffer, per-expert GEMMs over its slices and a
+            # deterministic combine (KF_MOE_NATIVE=0 takes the loop below)
+            out = ops.moe_experts(xf, logits, self.experts_w13,
+                                  self.experts_w2, cfg.top_k, self.e_lo)
+            if self.ep:
+                out = epmod.reduce_scatter_sum(out, self.ep)
+            return out.view(B, S, h)
         topv, topi = logits.topk(cfg.top_k, dim=-1)
         weights = torch.softmax(topv.float(), dim=-1).to(x.dtype)
         out = torch.zeros_like(xf)

@@ -9,11 +9,13 @@ Dispatch policy:
     so the full stack runs in CPU-only CI.
 
 All ops are exposed as autograd-capable functions:
-  rms_norm, rope, flash_attention, cross_entropy, fused_adamw (no autograd).
+  rms_norm, rope, flash_attention, cross_entropy, fused_adamw (no autograd),
+  moe_route / moe_gather / grouped_linear / moe_combine (the MoE block).
 """
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import os
 from typing import Optional
 
@@ -31,6 +33,8 @@ __all__ = [
     "masked_attention",
     "swiglu", "fused_qkv_attention",
     "rms_norm_residual", "grad_norm", "step_tail_enabled",
+    "MoeRouting", "moe_route", "moe_gather", "moe_combine", "grouped_linear",
+    "moe_experts", "moe_native_ok",
 ]
 
 rope_cos_sin = reference.rope_cos_sin
@@ -1217,3 +1221,316 @@ def fused_adamw(p16: torch.Tensor, p32: torch.Tensor, grad: torch.Tensor,
     p32.mul_(1 - lr * decay)
     p32.addcdiv_(m / bc1, denom, value=-lr)
     p16.copy_(p32.to(torch.bfloat16))
+
+
+# ------------------------------------------------------ Mixture of experts --
+
+MOE_MAX_EXPERTS = 64
+MOE_MAX_TOP_K = 8
+
+
+def _moe_native_enabled() -> bool:
+    """KF_MOE_NATIVE=0: bisection switch — MoEMLP runs its per-expert Python
+    loop (topk, nonzero, index_add_) instead of the moe.hip path."""
+    return os.environ.get("KF_MOE_NATIVE", "1") != "0"
+
+
+def moe_native_ok(x: torch.Tensor, n_experts: int, top_k: int) -> bool:
+    """True if MoEMLP takes the moe.hip path for token rows x [T, h]: a bf16
+    GPU tensor, the library loaded, KF_MOE_NATIVE != 0 and the shape within
+    the kernels' limits."""
+    return (x.is_cuda and x.dtype == torch.bfloat16 and _moe_native_enabled()
+            and 2 <= n_experts <= MOE_MAX_EXPERTS
+            and 1 <= top_k <= min(n_experts, MOE_MAX_TOP_K)
+            and x.shape[-1] % 8 == 0 and _use_native(x))
+
+
+def _moe_check(t: torch.Tensor, n_experts: int, top_k: int) -> None:
+    if not (2 <= n_experts <= MOE_MAX_EXPERTS
+            and 1 <= top_k <= min(n_experts, MOE_MAX_TOP_K)):
+        raise ValueError(
+            f"moe ops support 2 <= n_experts <= {MOE_MAX_EXPERTS} and "
+            f"1 <= top_k <= min(n_experts, {MOE_MAX_TOP_K}); got "
+            f"n_experts={n_experts}, top_k={top_k}")
+    if t.is_cuda and _backend.native_enabled() and t.dtype != torch.bfloat16:
+        raise ValueError(f"native moe ops need bf16 inputs, got {t.dtype}")
+
+
+@dataclasses.dataclass(frozen=True)
+class MoeRouting:
+    """The routing of one MoE layer, as ops.moe_route returns it.
+
+    topi int32 [T, k] expert of each slot (descending logit, lower index
+    first among equals); topw [T, k] gate weights (differentiable w.r.t. the
+    logits); probs fp32 [T, k], topw before rounding; pos int32 [T, k] row of
+    each (token, slot) pair in the permuted buffer, -1 if its expert is not
+    local; src int32 [T * k], src[pos[t, s]] = t (first `rows` entries);
+    offsets int32 [n_local + 1] first row of each local expert; splits: host
+    list, rows per local expert."""
+    topi: torch.Tensor
+    topw: torch.Tensor
+    probs: torch.Tensor
+    pos: torch.Tensor
+    src: torch.Tensor
+    offsets: torch.Tensor
+    splits: tuple
+    e_lo: int
+    n_local: int
+
+    @property
+    def rows(self) -> int:
+        """M: rows of the permuted buffer (pairs routed to a local expert)."""
+        return sum(self.splits)
+
+
+class _MoeRoute(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, top_k):
+        T, E = logits.shape
+        if _use_native(logits):
+            lib = _backend.require()
+            lg = logits.contiguous()
+            topi = torch.empty(T, top_k, dtype=torch.int32,
+                               device=logits.device)
+            probs = torch.empty(T, top_k, dtype=torch.float32,
+                                device=logits.device)
+            topw = torch.empty(T, top_k, dtype=logits.dtype,
+                               device=logits.device)
+            _backend.check(
+                lib.kf_moe_route(_p(topi), _fp(probs), _p(topw), _p(lg), T, E,
+                                 top_k, _stream()), "moe_route")
+        else:
+            topi, probs, topw = reference.moe_route(logits, top_k)
+            if topw is probs:  # fp32 logits: .to() returned the same tensor
+                topw = probs.clone()
+        ctx.save_for_backward(probs, topi)
+        ctx.n_experts = E
+        ctx.mark_non_differentiable(topi, probs)
+        return topw, topi, probs
+
+    @staticmethod
+    def backward(ctx, dw, _dtopi, _dprobs):
+        probs, topi = ctx.saved_tensors
+        T, k = topi.shape
+        E = ctx.n_experts
+        if _use_native(dw):
+            lib = _backend.require()
+            dw = dw.contiguous()
+            dlogits = torch.empty(T, E, dtype=dw.dtype, device=dw.device)
+            _backend.check(
+                lib.kf_moe_route_bwd(_p(dlogits), _p(dw), _fp(probs),
+                                     _p(topi), T, E, k, _stream()),
+                "moe_route_bwd")
+            return dlogits, None
+        return reference.moe_route_bwd(dw, probs, topi, E), None
+
+
+def _moe_sort(topi: torch.Tensor, e_lo: int, n_local: int):
+    T, k = topi.shape
+    if not _use_native(topi):
+        return reference.moe_sort(topi, e_lo, n_local)
+    lib = _backend.require()
+    dev = topi.device
+    pos = torch.empty(T, k, dtype=torch.int32, device=dev)
+    src = torch.empty(T * k, dtype=torch.int32, device=dev)
+    offsets = torch.empty(n_local + 1, dtype=torch.int32, device=dev)
+    work = torch.empty(int(lib.kf_moe_sort_nwork(T, k, n_local)),
+                       dtype=torch.int32, device=dev)
+    _backend.check(
+        lib.kf_moe_sort(_p(pos), _p(src), _p(offsets), _p(work), _p(topi), T,
+                        k, e_lo, n_local, _stream()), "moe_sort")
+    return pos, src, offsets
+
+
+def moe_route(logits: torch.Tensor, top_k: int, e_lo: int = 0,
+              n_local: Optional[int] = None) -> MoeRouting:
+    """Route T tokens: logits [T, E] -> MoeRouting for the local experts
+    [e_lo, e_lo + n_local) (default: all E).
+
+    The expert choice is that of a stable descending sort: among equal logits
+    the lower expert index wins, whatever the values (NaN, inf, all equal) the
+    k experts of a token are distinct and in range. routing.topw is the
+    softmax over the k selected logits (fp32 math) and carries the gradient
+    back to `logits`. The pairs are sorted by expert with a stable counting
+    sort, so the routing is a pure function of the logits.
+
+    `splits` is read from the device with one copy: the only host sync of an
+    MoE layer, and what sizes the [M, .] buffers exactly."""
+    if logits.dim() != 2:
+        raise ValueError(f"moe_route: logits must be [T, E], got "
+                         f"{tuple(logits.shape)}")
+    E = logits.shape[1]
+    top_k = int(top_k)
+    _moe_check(logits, E, top_k)
+    n_local = E - e_lo if n_local is None else int(n_local)
+    if not (0 <= e_lo and 1 <= n_local and e_lo + n_local <= E):
+        raise ValueError(f"moe_route: local expert range [{e_lo}, "
+                         f"{e_lo + n_local}) is not within [0, {E})")
+    topw, topi, probs = _MoeRoute.apply(logits, top_k)
+    pos, src, offsets = _moe_sort(topi, e_lo, n_local)
+    off = offsets.tolist()  # the one device-to-host copy
+    splits = tuple(off[i + 1] - off[i] for i in range(n_local))
+    return MoeRouting(topi, topw, probs, pos, src, offsets, splits, e_lo,
+                      n_local)
+
+
+class _MoeGather(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, src, pos, M):
+        T, h = x.shape
+        ctx.save_for_backward(pos)
+        ctx.dims = (T, h, M)
+        if _use_native(x):
+            lib = _backend.require()
+            x = x.contiguous()
+            xp = torch.empty(M, h, dtype=x.dtype, device=x.device)
+            _backend.check(
+                lib.kf_moe_gather(_p(xp), _p(x), _p(src), M, T, h, _stream()),
+                "moe_gather")
+            return xp
+        return reference.moe_gather(x, src, M)
+
+    @staticmethod
+    def backward(ctx, dxp):
+        (pos,) = ctx.saved_tensors
+        T, h, M = ctx.dims
+        if _use_native(dxp):
+            lib = _backend.require()
+            dxp = dxp.contiguous()
+            dx = torch.empty(T, h, dtype=dxp.dtype, device=dxp.device)
+            _backend.check(
+                lib.kf_moe_gather_bwd(_p(dx), _p(dxp), _p(pos), T,
+                                      pos.shape[1], h, M, _stream()),
+                "moe_gather_bwd")
+            return dx, None, None, None
+        return reference.moe_gather_bwd(dxp, pos), None, None, None
+
+
+def _moe_rows_check(t: torch.Tensor, routing: MoeRouting, rows: int,
+                    name: str) -> None:
+    if t.dim() != 2 or t.shape[0] != rows:
+        raise ValueError(f"{name}: expected [{rows}, h], got "
+                         f"{tuple(t.shape)}")
+    if _use_native(t) and (t.shape[1] % 8 or t.dtype != torch.bfloat16):
+        raise ValueError(f"{name}: the native path needs bf16 rows with "
+                         f"h % 8 == 0, got {t.dtype}, h={t.shape[1]}")
+
+
+def moe_gather(x: torch.Tensor, routing: MoeRouting) -> torch.Tensor:
+    """Dispatch: x [T, h] -> xp [M, h], xp[r] = x[routing.src[r]], the rows of
+    each local expert contiguous (routing.splits). A bit-exact row copy; its
+    backward sums each token's rows in fp32, in slot order, without
+    atomics."""
+    _moe_rows_check(x, routing, routing.pos.shape[0], "moe_gather")
+    return _MoeGather.apply(x, routing.src, routing.pos, routing.rows)
+
+
+class _MoeCombine(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, topw, pos):
+        M, h = y.shape
+        T, k = pos.shape
+        if _use_native(y):
+            lib = _backend.require()
+            y, topw = y.contiguous(), topw.contiguous()
+            out = torch.empty(T, h, dtype=y.dtype, device=y.device)
+            _backend.check(
+                lib.kf_moe_combine(_p(out), _p(y), _p(topw), _p(pos), T, k, h,
+                                   M, _stream()), "moe_combine")
+        else:
+            out = reference.moe_combine(y, topw, pos)
+        ctx.save_for_backward(y, topw, pos)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        y, topw, pos = ctx.saved_tensors
+        M, h = y.shape
+        T, k = pos.shape
+        if _use_native(dout):
+            lib = _backend.require()
+            dout = dout.contiguous()
+            dy = torch.empty_like(y)  # every row < M is written exactly once
+            dw = torch.empty_like(topw)
+            _backend.check(
+                lib.kf_moe_combine_bwd(_p(dy), _p(dw), _p(dout), _p(y),
+                                       _p(topw), _p(pos), T, k, h, M,
+                                       _stream()), "moe_combine_bwd")
+            return dy, dw, None
+        dy, dw = reference.moe_combine_bwd(dout, y, topw, pos)
+        return dy, dw, None
+
+
+def moe_combine(y: torch.Tensor, routing: MoeRouting) -> torch.Tensor:
+    """Combine: y [M, h] (expert outputs in permuted order) -> out [T, h],
+    out[t] = sum_s topw[t, s] * y[pos[t, s]] in fp32, ascending slot order,
+    rounded once. A token with no local expert gets zeros. Gradients flow to
+    y and to routing.topw; the same inputs give the same bits."""
+    _moe_rows_check(y, routing, routing.rows, "moe_combine")
+    topw = routing.topw
+    if topw.dtype != y.dtype:
+        topw = topw.to(y.dtype)
+    return _MoeCombine.apply(y, topw, routing.pos)
+
+
+class _GroupedLinear(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xp, w_bank, splits):
+        out = torch.empty(xp.shape[0], w_bank.shape[1], dtype=xp.dtype,
+                          device=xp.device)
+        o = 0
+        for e, n in enumerate(splits):
+            if n:
+                torch.mm(xp[o:o + n], w_bank[e].t(), out=out[o:o + n])
+            o += n
+        ctx.save_for_backward(xp, w_bank)
+        ctx.splits = splits
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        xp, w_bank = ctx.saved_tensors
+        dout = dout.contiguous()
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dxp = torch.empty_like(xp) if need_x else None
+        dw = torch.empty_like(w_bank) if need_w else None
+        o = 0
+        for e, n in enumerate(ctx.splits):
+            if n == 0:
+                if need_w:
+                    dw[e].zero_()
+                continue
+            if need_x:
+                torch.mm(dout[o:o + n], w_bank[e], out=dxp[o:o + n])
+            if need_w:
+                torch.mm(dout[o:o + n].t(), xp[o:o + n], out=dw[e])
+            o += n
+        return dxp, dw, None
+
+
+def grouped_linear(xp: torch.Tensor, w_bank: torch.Tensor,
+                   splits) -> torch.Tensor:
+    """Per-expert linear over one permuted buffer: xp [M, in], w_bank
+    [n, out, in], splits n row counts summing to M ->
+    out[off_e : off_e + n_e] = xp[off_e : off_e + n_e] @ w_bank[e].T, written
+    into one preallocated [M, out]. Library GEMMs over contiguous slices; the
+    backward loops the same slices (dW[e] is zeros for an empty expert)."""
+    splits = tuple(int(n) for n in splits)
+    if (xp.dim() != 2 or w_bank.dim() != 3 or len(splits) != w_bank.shape[0]
+            or sum(splits) != xp.shape[0] or xp.shape[1] != w_bank.shape[2]):
+        raise ValueError(
+            f"grouped_linear: xp {tuple(xp.shape)}, w_bank "
+            f"{tuple(w_bank.shape)} and splits {splits} do not agree")
+    return _GroupedLinear.apply(xp, w_bank, splits)
+
+
+def moe_experts(x: torch.Tensor, logits: torch.Tensor, w13: torch.Tensor,
+                w2: torch.Tensor, top_k: int, e_lo: int = 0) -> torch.Tensor:
+    """The routed expert block on token rows: x [T, h], router logits [T, E],
+    local expert banks w13 [n, 2f, h] and w2 [n, h, f] for experts
+    [e_lo, e_lo + n) -> [T, h]. route, sort, gather, grouped w13 GEMMs, one
+    swiglu over the whole [M, 2f] buffer, grouped w2 GEMMs, combine."""
+    routing = moe_route(logits, top_k, e_lo, w13.shape[0])
+    xp = moe_gather(x, routing)
+    a = swiglu(grouped_linear(xp, w13, routing.splits))
+    return moe_combine(grouped_linear(a, w2, routing.splits), routing)

@@ -133,9 +133,19 @@ SIGNATURES: dict[str, list] = {
                             [_F, _P],
     "kf_attn64_bwd_varlen": _BWD_HEAD[:10] + [_PI32] + [_I64] * 6 + [_F, _P],
     "kf_attn_decode": [_P] * 6 + [_PI32, _PI32] + [_I64] * 6 + [_F, _P],
+    # mixture of experts (moe.hip): ..., T, E | k | h ..., stream
+    "kf_moe_route": [_P, _FP, _P, _P, _I64, _I64, _I64, _P],
+    "kf_moe_route_bwd": [_P, _P, _FP, _P, _I64, _I64, _I64, _P],
+    "kf_moe_sort_nwork": [_I64, _I64, _I64],
+    # pos, src, offsets, work, topi, T, k, e_lo, n_local, stream
+    "kf_moe_sort": [_P] * 5 + [_I64] * 4 + [_P],
+    "kf_moe_gather": [_P, _P, _P, _I64, _I64, _I64, _P],       # M, T, h
+    "kf_moe_gather_bwd": [_P, _P, _P] + [_I64] * 4 + [_P],     # T, k, h, M
+    "kf_moe_combine": [_P] * 4 + [_I64] * 4 + [_P],
+    "kf_moe_combine_bwd": [_P] * 6 + [_I64] * 4 + [_P],
 }
 _RETURNS_INT64 = ("kf_rmsnorm_bwd_nparts", "kf_layernorm_bwd_nparts",
-                  "kf_grad_sumsq_nparts")
+                  "kf_grad_sumsq_nparts", "kf_moe_sort_nwork")
 
 
 def _configure(lib: ctypes.CDLL) -> None:

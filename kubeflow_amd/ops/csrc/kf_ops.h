@@ -165,6 +165,31 @@ KF_EXPORT int kf_attn64_bwd_varlen(void* dq, void* dk, void* dv,
     int64_t B, int64_t S, int64_t Hq, int64_t Hkv, int64_t qts, int64_t kts,
     float scale, void* stream);
 
+// ---- mixture-of-experts routing, dispatch, combine (moe.hip) ----
+// T tokens, E experts, k = top_k, h hidden, M rows of the permuted buffer.
+// topi / pos int32 [T, k], src int32 [T * k], offsets int32 [n_local + 1],
+// probs fp32 [T, k], topw / dw bf16 [T, k]; work int32
+// [kf_moe_sort_nwork(T, k, n_local)]. 2 <= E <= 64, k <= min(E, 8), h % 8 == 0.
+KF_EXPORT int kf_moe_route(void* topi, float* probs, void* topw,
+    const void* logits, int64_t T, int64_t E, int64_t k, void* stream);
+KF_EXPORT int kf_moe_route_bwd(void* dlogits, const void* dw,
+    const float* probs, const void* topi, int64_t T, int64_t E, int64_t k,
+    void* stream);
+KF_EXPORT int64_t kf_moe_sort_nwork(int64_t T, int64_t k, int64_t n_local);
+KF_EXPORT int kf_moe_sort(void* pos, void* src, void* offsets, void* work,
+    const void* topi, int64_t T, int64_t k, int64_t e_lo, int64_t n_local,
+    void* stream);
+KF_EXPORT int kf_moe_gather(void* xp, const void* x, const void* src,
+    int64_t M, int64_t T, int64_t h, void* stream);
+KF_EXPORT int kf_moe_gather_bwd(void* dx, const void* dxp, const void* pos,
+    int64_t T, int64_t k, int64_t h, int64_t M, void* stream);
+KF_EXPORT int kf_moe_combine(void* out, const void* y, const void* topw,
+    const void* pos, int64_t T, int64_t k, int64_t h, int64_t M,
+    void* stream);
+KF_EXPORT int kf_moe_combine_bwd(void* dy, void* dw, const void* dout,
+    const void* y, const void* topw, const void* pos, int64_t T, int64_t k,
+    int64_t h, int64_t M, void* stream);
+
 // ---- decode attention over the KV cache (attention_decode.hip) ----
 KF_EXPORT int kf_attn_decode(void* out, void* part_o, void* part_ml,
     const void* q, const void* kcache, const void* vcache, const int* slots,

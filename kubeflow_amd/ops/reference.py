@@ -107,3 +107,108 @@ def adamw_step(p32: torch.Tensor, g: torch.Tensor, m: torch.Tensor,
     denom = (v / bc2).sqrt_().add_(eps)
     p32.mul_(1 - lr * weight_decay)
     p32.addcdiv_(m / bc1, denom, value=-lr)
+
+
+# ---------------------------------------------------- mixture of experts --
+#
+# The semantics of csrc/moe.hip in plain torch: the CPU path of the public
+# ops and the oracle of the GPU tests. T tokens, E experts, k = top_k; the
+# local expert range is [e_lo, e_lo + n_local) and M pairs (token, slot) are
+# routed into it. Every sum over a token's slots is an fp32 loop in ascending
+# slot order starting from 0, skipping slots whose expert is not local, so
+# that the kernels can be compared bit for bit.
+
+def moe_route(logits: torch.Tensor, top_k: int):
+    """logits [T, E] -> (topi int32 [T, k], probs fp32 [T, k], topw [T, k] in
+    logits.dtype). Slots by descending logit; among equal logits the lower
+    expert index first (a stable descending sort, NaN sorting first as in
+    torch.sort). probs is the fp32 softmax over the k selected logits."""
+    vals, idx = torch.sort(logits, dim=-1, descending=True, stable=True)
+    probs = torch.softmax(vals[:, :top_k].float(), dim=-1)
+    return idx[:, :top_k].to(torch.int32), probs, probs.to(logits.dtype)
+
+
+def moe_route_bwd(dw: torch.Tensor, probs: torch.Tensor, topi: torch.Tensor,
+                  n_experts: int) -> torch.Tensor:
+    """dlogits [T, E] in dw.dtype: p_i * (dw_i - sum_j p_j dw_j) at column
+    topi[t, i], exact zeros elsewhere."""
+    d = dw.float()
+    g = probs * (d - (probs * d).sum(dim=-1, keepdim=True))
+    out = torch.zeros(dw.shape[0], n_experts, dtype=torch.float32,
+                      device=dw.device)
+    out.scatter_(1, topi.long(), g)
+    return out.to(dw.dtype)
+
+
+def moe_sort(topi: torch.Tensor, e_lo: int, n_local: int):
+    """Stable counting sort of the (token, slot) pairs by expert ->
+    (pos int32 [T, k], src int32 [T * k], offsets int32 [n_local + 1]).
+    pos[t, s] is the pair's row in the permuted buffer (-1: expert not
+    local), src[pos[t, s]] = t, offsets[el] the first row of local expert el
+    and offsets[n_local] = M. Only src[:M] is defined."""
+    T, k = topi.shape
+    flat = topi.reshape(-1).long() - e_lo
+    local = (flat >= 0) & (flat < n_local)
+    key = torch.where(local, flat, torch.full_like(flat, n_local))
+    order = torch.argsort(key, stable=True)
+    pos = torch.empty(T * k, dtype=torch.int64, device=topi.device)
+    pos[order] = torch.arange(T * k, device=topi.device)
+    pos[~local] = -1
+    src = torch.zeros(T * k, dtype=torch.int32, device=topi.device)
+    m = int(local.sum())
+    src[:m] = (order[:m] // k).to(torch.int32)
+    counts = torch.bincount(key[local], minlength=n_local)[:n_local]
+    offsets = torch.zeros(n_local + 1, dtype=torch.int64, device=topi.device)
+    offsets[1:] = torch.cumsum(counts, 0)
+    return (pos.view(T, k).to(torch.int32), src, offsets.to(torch.int32))
+
+
+def moe_gather(x: torch.Tensor, src: torch.Tensor, m: int) -> torch.Tensor:
+    """xp[r] = x[src[r]], r < m."""
+    return x[src[:m].long()]
+
+
+def _moe_slot_sum(rows: torch.Tensor, pos: torch.Tensor, w, dtype):
+    T, k = pos.shape
+    acc = torch.zeros(T, rows.shape[1], dtype=torch.float32,
+                      device=rows.device)
+    if rows.shape[0] == 0:
+        return acc.to(dtype)
+    for s in range(k):
+        p = pos[:, s].long()
+        term = rows[p.clamp_min(0)].float()
+        if w is not None:
+            term = w[:, s:s + 1].float() * term
+        acc = torch.where((p >= 0).unsqueeze(1), acc + term, acc)
+    return acc.to(dtype)
+
+
+def moe_gather_bwd(dxp: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
+    """dx[t] = sum_s dxp[pos[t, s]] (fp32, slot order), in dxp.dtype."""
+    return _moe_slot_sum(dxp, pos, None, dxp.dtype)
+
+
+def moe_combine(y: torch.Tensor, topw: torch.Tensor,
+                pos: torch.Tensor) -> torch.Tensor:
+    """out[t] = sum_s topw[t, s] * y[pos[t, s]] (fp32, slot order), in
+    y.dtype."""
+    return _moe_slot_sum(y, pos, topw, y.dtype)
+
+
+def moe_combine_bwd(dout: torch.Tensor, y: torch.Tensor, topw: torch.Tensor,
+                    pos: torch.Tensor):
+    """(dy [M, h], dw [T, k]): dy[pos[t, s]] = topw[t, s] * dout[t] and
+    dw[t, s] = <dout[t], y[pos[t, s]]> in fp32, 0 for a slot that is not
+    local; both rounded to y.dtype."""
+    T, k = pos.shape
+    dy = torch.zeros_like(y)
+    dw = torch.zeros(T, k, dtype=torch.float32, device=y.device)
+    d32 = dout.float()
+    for s in range(k):
+        p = pos[:, s].long()
+        sel = (p >= 0).nonzero(as_tuple=True)[0]
+        if sel.numel() == 0:
+            continue
+        dy[p[sel]] = (topw[sel, s:s + 1].float() * d32[sel]).to(y.dtype)
+        dw[sel, s] = (d32[sel] * y[p[sel]].float()).sum(dim=-1)
+    return dy, dw.to(topw.dtype)

@@ -36,7 +36,7 @@ __all__ = [
     "rope_oracle",
     "rms_norm_oracle", "layer_norm_oracle", "swiglu_oracle",
     "cross_entropy_oracle", "adamw_oracle", "decode_oracle",
-    "linear_residual_oracle",
+    "linear_residual_oracle", "moe_mlp_oracle", "moe_mlp_emulated",
 ]
 
 
@@ -380,3 +380,69 @@ def linear_residual_oracle(x, w, residual=None):
     """fp32 x @ w^T (+ residual)."""
     y = torch.nn.functional.linear(_f32(x), _f32(w))
     return y if residual is None else y + _f32(residual)
+
+
+# ------------------------------------------------------- mixture of experts
+
+class _RoundBf16(torch.autograd.Function):
+    """'Held in bf16' in both directions: the value and its gradient."""
+
+    @staticmethod
+    def forward(ctx, t):
+        return _bf(t)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _bf(g)
+
+
+def _moe_block(x, gate_w, w13, w2, topi, dout, e_lo, rnd):
+    """One MoE block with the routing given: topi [T, k] picks the experts,
+    everything else (the logits, the gate weights as the softmax over the
+    selected logits, the experts, the weighted sum in slot order) is computed
+    here. `rnd` is applied where the bf16 model path holds a tensor in bf16.
+    Returns out, dx, dgate, dw13, dw2 (fp32)."""
+    xr, gr, w13r, w2r = (_f32(t).clone().requires_grad_(True)
+                         for t in (x, gate_w, w13, w2))
+    topi = topi.detach().cpu().long()
+    T, k = topi.shape
+    # x feeds the router and the experts; the two gradients are held in bf16
+    # before autograd adds them
+    logits = rnd(rnd(xr) @ gr.t())
+    topw = rnd(torch.softmax(logits.gather(1, topi), dim=-1))
+    xe = rnd(xr)
+    out = torch.zeros(T, xr.shape[1])
+    for s in range(k):
+        ys = torch.zeros(T, xr.shape[1])
+        for el in range(w13r.shape[0]):
+            sel = (topi[:, s] == e_lo + el).nonzero(as_tuple=True)[0]
+            if sel.numel() == 0:
+                continue
+            h13 = rnd(xe[sel] @ w13r[el].t())
+            g, u = h13.chunk(2, dim=-1)
+            a = rnd(torch.nn.functional.silu(g) * u)
+            ys = ys.index_copy(0, sel, rnd(a @ w2r[el].t()))
+        out = out + topw[:, s:s + 1] * ys
+    out = rnd(out)
+    out.backward(_f32(dout))
+    return (out.detach(), rnd(xr.grad), rnd(gr.grad), rnd(w13r.grad),
+            rnd(w2r.grad))
+
+
+def moe_mlp_oracle(x, gate_w, w13, w2, topi, dout, e_lo: int = 0):
+    """(out, dx, dgate, dw13, dw2) of one MoE block in fp32, routing given:
+    x [T, h], gate_w [E, h], w13 [n, 2f, h], w2 [n, h, f] the banks of
+    experts [e_lo, e_lo + n), topi [T, k]. The gate weights are the softmax
+    over the k selected logits, so dx and dgate include the router path."""
+    return _moe_block(x, gate_w, w13, w2, topi, dout, e_lo, lambda t: t)
+
+
+def moe_mlp_emulated(x, gate_w, w13, w2, topi, dout, e_lo: int = 0):
+    """moe_mlp_oracle's math with a bf16 round (of the value and of its
+    gradient) after every GEMM, after the softmax, after swiglu and after the
+    weighted sum, and of every returned gradient. The kernels round at the
+    same places but accumulate in fp32 between them and compute swiglu and
+    the softmax from unrounded fp32 intermediates, so this rounds strictly
+    more: the envelope that sets the per-row bound."""
+    return _moe_block(x, gate_w, w13, w2, topi, dout, e_lo,
+                      _RoundBf16.apply)
