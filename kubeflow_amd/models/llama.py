@@ -131,7 +131,9 @@ class MoEMLP(nn.Module):
     On the GPU (bf16, library loaded, KF_MOE_NATIVE != 0, E <= 64, k <= 8)
     the routed block is ops.moe_experts: moe.hip routing, dispatch and
     combine around per-expert library GEMMs, reproducible bit for bit. Every
-    other case runs the per-expert loop in forward()."""
+    other case runs the per-expert loop in forward(). The serving decode step
+    calls decode_routed (ops.moe_experts_decode: no host sync, so it
+    captures into a graph) or decode_dense instead of forward()."""
 
     def __init__(self, cfg: LlamaConfig, ep=None):
         super().__init__()
@@ -211,6 +213,38 @@ class MoEMLP(nn.Module):
             y = ops.swiglu(ops.skinny_linear(xf, self.experts_w13[el]))
             y = ops.skinny_linear(y, self.experts_w2[el])
             out = out + gatew[:, self.e_lo + el].unsqueeze(1) * y
+        return out.view(N, S, h)
+
+    def routed_decode_ok(self, x, q8: bool = False) -> bool:
+        """True if decode_routed(x) takes ops.moe_experts_decode: EP = 1, the
+        moe.hip path usable for x's rows (bf16 on the GPU), at most 32 rows
+        and both banks within the grouped skinny kernels' shapes."""
+        cfg = self.cfg
+        h, f = cfg.hidden_size, cfg.ffn_dim
+        T = x.numel() // max(1, x.shape[-1])
+        return (self.ep is None
+                and ops.moe_native_ok(x.reshape(T, -1), cfg.n_experts,
+                                      cfg.top_k)
+                and self.experts_w13.dtype == x.dtype
+                and self.gate.weight.dtype == x.dtype
+                and ops.grouped_skinny_ok(T, 2 * f, h, x.dtype, q8=q8)
+                and ops.grouped_skinny_ok(T, h, f, x.dtype, q8=q8))
+
+    def decode_routed(self, x, q8=None):
+        """Capture-safe routed decode: only the k experts a token selects run
+        on it, and an expert no token selects streams none of its weights.
+        ops.moe_experts_decode keeps the expert offsets on the device, so a
+        captured graph follows each replay's routing. q8: the two banks
+        quantized per row (see ops.moe_experts_decode). Where
+        routed_decode_ok does not hold (the CPU, EP, more than 32 rows, bank
+        shapes the kernels reject) this is decode_dense on the bf16 banks."""
+        if not self.routed_decode_ok(x, q8=q8 is not None):
+            return self.decode_dense(x)
+        N, S, h = x.shape
+        xf = x.reshape(N * S, h)
+        logits = torch.nn.functional.linear(xf, self.gate.weight)
+        out = ops.moe_experts_decode(xf, logits, self.experts_w13,
+                                     self.experts_w2, self.cfg.top_k, q8=q8)
         return out.view(N, S, h)
 
 

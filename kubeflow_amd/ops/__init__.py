@@ -10,7 +10,9 @@ Dispatch policy:
 
 All ops are exposed as autograd-capable functions:
   rms_norm, rope, flash_attention, cross_entropy, fused_adamw (no autograd),
-  moe_route / moe_gather / grouped_linear / moe_combine (the MoE block).
+  moe_route / moe_gather / grouped_linear / moe_combine (the MoE block);
+  grouped_skinny_linear / moe_experts_decode (its decode form: inference
+  only, no host sync).
 """
 from __future__ import annotations
 
@@ -35,6 +37,8 @@ __all__ = [
     "rms_norm_residual", "grad_norm", "step_tail_enabled",
     "MoeRouting", "moe_route", "moe_gather", "moe_combine", "grouped_linear",
     "moe_experts", "moe_native_ok",
+    "grouped_skinny_ok", "grouped_skinny_linear", "grouped_skinny_linear_q8",
+    "moe_experts_decode",
 ]
 
 rope_cos_sin = reference.rope_cos_sin
@@ -1266,7 +1270,8 @@ class MoeRouting:
     each (token, slot) pair in the permuted buffer, -1 if its expert is not
     local; src int32 [T * k], src[pos[t, s]] = t (first `rows` entries);
     offsets int32 [n_local + 1] first row of each local expert; splits: host
-    list, rows per local expert."""
+    list, rows per local expert, or None from moe_route(sync=False), where
+    every expert is local and the permuted buffer has all T * k rows."""
     topi: torch.Tensor
     topw: torch.Tensor
     probs: torch.Tensor
@@ -1280,6 +1285,8 @@ class MoeRouting:
     @property
     def rows(self) -> int:
         """M: rows of the permuted buffer (pairs routed to a local expert)."""
+        if self.splits is None:
+            return self.pos.numel()
         return sum(self.splits)
 
 
@@ -1343,7 +1350,7 @@ def _moe_sort(topi: torch.Tensor, e_lo: int, n_local: int):
 
 
 def moe_route(logits: torch.Tensor, top_k: int, e_lo: int = 0,
-              n_local: Optional[int] = None) -> MoeRouting:
+              n_local: Optional[int] = None, sync: bool = True) -> MoeRouting:
     """Route T tokens: logits [T, E] -> MoeRouting for the local experts
     [e_lo, e_lo + n_local) (default: all E).
 
@@ -1355,7 +1362,12 @@ def moe_route(logits: torch.Tensor, top_k: int, e_lo: int = 0,
     sort, so the routing is a pure function of the logits.
 
     `splits` is read from the device with one copy: the only host sync of an
-    MoE layer, and what sizes the [M, .] buffers exactly."""
+    MoE layer, and what sizes the [M, .] buffers exactly.
+
+    sync=False skips that copy (splits is None), so the call can be captured
+    in a graph. It is legal only when the local range is all E experts: then
+    M = T * k whatever the logits, and `offsets` stays on the device for
+    grouped_skinny_linear."""
     if logits.dim() != 2:
         raise ValueError(f"moe_route: logits must be [T, E], got "
                          f"{tuple(logits.shape)}")
@@ -1366,8 +1378,15 @@ def moe_route(logits: torch.Tensor, top_k: int, e_lo: int = 0,
     if not (0 <= e_lo and 1 <= n_local and e_lo + n_local <= E):
         raise ValueError(f"moe_route: local expert range [{e_lo}, "
                          f"{e_lo + n_local}) is not within [0, {E})")
+    if not sync and (e_lo != 0 or n_local != E):
+        raise ValueError(
+            f"moe_route: sync=False needs all {E} experts local (the row "
+            f"count is then T * k), got [{e_lo}, {e_lo + n_local})")
     topw, topi, probs = _MoeRoute.apply(logits, top_k)
     pos, src, offsets = _moe_sort(topi, e_lo, n_local)
+    if not sync:
+        return MoeRouting(topi, topw, probs, pos, src, offsets, None, e_lo,
+                          n_local)
     off = offsets.tolist()  # the one device-to-host copy
     splits = tuple(off[i + 1] - off[i] for i in range(n_local))
     return MoeRouting(topi, topw, probs, pos, src, offsets, splits, e_lo,
@@ -1534,3 +1553,160 @@ def moe_experts(x: torch.Tensor, logits: torch.Tensor, w13: torch.Tensor,
     xp = moe_gather(x, routing)
     a = swiglu(grouped_linear(xp, w13, routing.splits))
     return moe_combine(grouped_linear(a, w2, routing.splits), routing)
+
+
+# ----------------------------------------------------- Routed MoE decode --
+
+GROUPED_SKINNY_MAX_ROWS = 32
+
+
+def grouped_skinny_ok(T: int, N: int, K: int, dtype,
+                      q8: bool = False) -> bool:
+    """True if kf_skinny_gemm_grouped (q8: kf_skinny_gemm_grouped_q8) takes
+    T token rows against [., N, K] banks: what a caller asks before it
+    captures a graph, since the fallback of grouped_skinny_linear syncs. The
+    LDS kernel needs K % 512 == 0 (q8: K % 1024 == 0) and T <= 32, the direct
+    bf16 kernel K % 32 == 0 and T <= 16."""
+    if (dtype != torch.bfloat16 or not 1 <= T <= GROUPED_SKINNY_MAX_ROWS
+            or N < 16 or N % 16 or K < 32):
+        return False
+    if q8:
+        return K % 1024 == 0
+    return K % 512 == 0 or (K % 32 == 0 and T <= 16)
+
+
+def _grouped_skinny(x, w, scale, offsets, max_rows, rows, out, n, N, K):
+    """Shared body of the two grouped linears; scale None = bf16 bank."""
+    name = "grouped_skinny_linear" + ("" if scale is None else "_q8")
+    if (x.dim() != 2 or x.shape[1] != K or offsets.dim() != 1
+            or offsets.numel() != n + 1
+            or (rows is not None and rows.dim() != 1)):
+        raise ValueError(
+            f"{name}: x {tuple(x.shape)}, bank [{n}, {N}, {K}], offsets "
+            f"{tuple(offsets.shape)} and rows "
+            f"{None if rows is None else tuple(rows.shape)} do not agree")
+    total = x.shape[0] if rows is None else rows.numel()
+    if out is not None and (out.dim() != 2 or out.shape[0] < total
+                            or out.shape[1] != N or out.dtype != x.dtype
+                            or not out.is_contiguous()):
+        raise ValueError(f"{name}: out must be a contiguous [>= {total}, "
+                         f"{N}] {x.dtype} tensor, got {tuple(out.shape)}")
+    max_rows = int(max_rows)
+    native = (_use_native(x) and offsets.dtype == torch.int32
+              and (rows is None or rows.dtype == torch.int32)
+              and grouped_skinny_ok(max_rows, N, K, x.dtype,
+                                    q8=scale is not None))
+    if not native:
+        wb = w if scale is None else dequantize_fp8_rows(w, scale, x.dtype)
+        y = reference.grouped_linear_offsets(x, wb.reshape(n, N, K), offsets,
+                                             rows)
+        if out is None:
+            return y
+        out[:total].copy_(y)
+        return out
+    lib = _backend.require()
+    x = x.contiguous()
+    offsets = offsets.contiguous()
+    if rows is not None:
+        rows = rows.contiguous()
+    if out is None:
+        out = torch.empty(total, N, dtype=x.dtype, device=x.device)
+    if scale is None:
+        _backend.check(
+            lib.kf_skinny_gemm_grouped(
+                _p(out), _p(x), _p(w), _i32p(offsets), _i32p(rows), n,
+                max_rows, total, x.shape[0], N, K, _stream()),
+            "skinny_gemm_grouped")
+    else:
+        _backend.check(
+            lib.kf_skinny_gemm_grouped_q8(
+                _p(out), _p(x), _p(w), _fp(scale), _i32p(offsets),
+                _i32p(rows), n, max_rows, total, x.shape[0], N, K,
+                _stream()),
+            "skinny_gemm_grouped_q8")
+    return out
+
+
+def grouped_skinny_linear(x: torch.Tensor, w_bank: torch.Tensor,
+                          offsets: torch.Tensor, max_rows: int,
+                          rows: Optional[torch.Tensor] = None, *,
+                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per-expert decode linear over device offsets: w_bank [n, N, K],
+    offsets int32 [n + 1] (MoeRouting.offsets, left on the device) ->
+    y [R, N], y[lo_e + i] = x[rows[lo_e + i] if rows is given else lo_e + i]
+    @ w_bank[e].T for i < offsets[e + 1] - lo_e. R is rows.numel(), else
+    x.shape[0]; rows at or past offsets[n] are not written.
+
+    One launch of kf_skinny_gemm_grouped (skinny_gemm.hip), no host sync, so
+    it captures into a graph and the replay follows the offsets of the day.
+    An expert without rows reads none of its weights. max_rows bounds the
+    rows of one expert (the decode token count T: a token's experts are
+    distinct); the kernel clamps to it. `rows` (int32, e.g. MoeRouting.src)
+    reads token rows of x in place of a gathered copy. `out`: a contiguous
+    [>= R, N] buffer to write rows [0, R) of. Each expert's rows are, bit for
+    bit, skinny_linear's for the same rows and w_bank[e].
+
+    Inference only (no autograd). Off the GPU and for shapes
+    grouped_skinny_ok rejects, reference.grouped_linear_offsets runs
+    instead; that path reads offsets on the host and is not for capture."""
+    if w_bank.dim() != 3:
+        raise ValueError("grouped_skinny_linear: w_bank must be [n, N, K], "
+                         f"got {tuple(w_bank.shape)}")
+    n, N, K = w_bank.shape
+    if _use_native(x) and (w_bank.dtype != x.dtype
+                           or not w_bank.is_contiguous()):
+        raise ValueError("grouped_skinny_linear: w_bank must be contiguous "
+                         f"and of x's dtype, got {w_bank.dtype}")
+    return _grouped_skinny(x, w_bank, None, offsets, max_rows, rows, out, n,
+                           N, K)
+
+
+def grouped_skinny_linear_q8(x: torch.Tensor, w8: torch.Tensor,
+                             scale: torch.Tensor, offsets: torch.Tensor,
+                             max_rows: int,
+                             rows: Optional[torch.Tensor] = None, *,
+                             out: Optional[torch.Tensor] = None
+                             ) -> torch.Tensor:
+    """grouped_skinny_linear on a quantized bank: w8 uint8 [n * N, K] and
+    scale fp32 [n * N], quantize_fp8_rows of the bank flattened to rows
+    (expert e, column j is row e * N + j); n = offsets.numel() - 1. Each
+    expert's rows are skinny_linear_q8's on the bank slice, bit for bit."""
+    n = offsets.numel() - 1
+    if (w8.dim() != 2 or n < 1 or w8.shape[0] % n or w8.dtype != torch.uint8
+            or scale.shape != (w8.shape[0],) or scale.dtype != torch.float32
+            or not w8.is_contiguous() or not scale.is_contiguous()):
+        raise ValueError(
+            f"grouped_skinny_linear_q8: w8 {tuple(w8.shape)} {w8.dtype}, "
+            f"scale {tuple(scale.shape)} {scale.dtype} and {n} experts do "
+            "not agree")
+    return _grouped_skinny(x, w8, scale, offsets, max_rows, rows, out, n,
+                           w8.shape[0] // n, w8.shape[1])
+
+
+@torch.no_grad()
+def moe_experts_decode(x: torch.Tensor, logits: torch.Tensor,
+                       w13: torch.Tensor, w2: torch.Tensor, top_k: int,
+                       q8=None) -> torch.Tensor:
+    """moe_experts for the decode step, without a host sync: x [T, h],
+    logits [T, E], full banks w13 [E, 2f, h] and w2 [E, h, f] -> [T, h].
+
+    moe_route(sync=False); the grouped w13 GEMM reading x through routing.src
+    (no gather launch, no permuted copy of x); one swiglu over [T * k, 2f];
+    the grouped w2 GEMM; moe_combine. Every buffer is sized from T, k and the
+    weight shapes, so a graph captured on one routing replays any other.
+    q8 = ((w13_8, w13_scale), (w2_8, w2_scale)), the banks through
+    quantize_fp8_rows on their [E * out, in] views, selects the fp8 kernels.
+    Inference only. For capture the caller checks grouped_skinny_ok for both
+    banks first."""
+    T = x.shape[0]
+    routing = moe_route(logits, top_k, 0, w13.shape[0], sync=False)
+    if q8 is None:
+        h13 = grouped_skinny_linear(x, w13, routing.offsets, T, routing.src)
+        y = grouped_skinny_linear(swiglu(h13), w2, routing.offsets, T)
+    else:
+        (w13_8, s13), (w2_8, s2) = q8
+        h13 = grouped_skinny_linear_q8(x, w13_8, s13, routing.offsets, T,
+                                       routing.src)
+        y = grouped_skinny_linear_q8(swiglu(h13), w2_8, s2, routing.offsets,
+                                     T)
+    return moe_combine(y, routing)

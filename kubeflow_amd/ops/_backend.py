@@ -105,6 +105,11 @@ SIGNATURES: dict[str, list] = {
     "kf_ce_bwd": [_P, _P, _FP, _PI64, _FP, _I64, _I64, _I64, _P],
     "kf_skinny_gemm": [_P, _P, _P, _P] + [_I64] * 6 + [_P],
     "kf_skinny_gemm_q8": [_P, _P, _P, _FP, _P] + [_I64] * 6 + [_P],
+    # c, a, w_bank | w8, wscale, offsets, a_rows, n_groups, max_rows,
+    # total_rows, a_nrows, N, K, stream
+    "kf_skinny_gemm_grouped": [_P, _P, _P, _PI32, _PI32] + [_I64] * 6 + [_P],
+    "kf_skinny_gemm_grouped_q8": [_P, _P, _P, _FP, _PI32, _PI32] +
+                                 [_I64] * 6 + [_P],
     "kf_kv_store": [_P] * 6 + [_I64, _I64, _I64, _P],
     "kf_decode_rope_store": [_P, _P, _P, _P, _FP, _FP, _PI32, _P] +
                             [_I64] * 5 + [_P],

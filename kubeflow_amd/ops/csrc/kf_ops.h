@@ -74,6 +74,16 @@ KF_EXPORT int kf_skinny_gemm(void* c, const void* a, const void* w,
 KF_EXPORT int kf_skinny_gemm_q8(void* c, const void* a, const void* w8,
     const float* wscale, const void* res, int64_t M, int64_t N, int64_t K,
     int64_t lda, int64_t ldw, int64_t ldc, void* stream);
+// grouped over device offsets (routed MoE decode): group e owns rows
+// [offsets[e], offsets[e+1]) of c and reads a through a_rows (nullable)
+KF_EXPORT int kf_skinny_gemm_grouped(void* c, const void* a,
+    const void* w_bank, const int* offsets, const int* a_rows,
+    int64_t n_groups, int64_t max_rows, int64_t total_rows, int64_t a_nrows,
+    int64_t N, int64_t K, void* stream);
+KF_EXPORT int kf_skinny_gemm_grouped_q8(void* c, const void* a,
+    const void* w8, const float* wscale, const int* offsets,
+    const int* a_rows, int64_t n_groups, int64_t max_rows,
+    int64_t total_rows, int64_t a_nrows, int64_t N, int64_t K, void* stream);
 KF_EXPORT int kf_kv_store(void* ck, void* cv, const void* k, const void* v,
     const void* slots, const void* positions, int64_t smax, int64_t row,
     int64_t n, void* stream);

@@ -406,3 +406,402 @@ KF_EXPORT int kf_skinny_gemm(void* c, const void* a, const void* w,
                        ldc);
   return (int)hipGetLastError();
 }
+
+// ---------------------------------------------------------------------
+// Grouped variants for routed MoE decode: one launch runs every expert's
+// skinny GEMM over the permuted [total_rows, .] buffer,
+//   lo = offsets[e], m = offsets[e+1] - lo
+//   c[lo + i, :] = a[a_rows ? a_rows[lo + i] : lo + i, :] @ w_bank[e]^T
+// with grid = (N/16, n_groups), so the expert index is block-uniform and
+// each block reads its two offsets itself (the int32 array kf_moe_sort
+// writes): nothing is read back to the host, and a captured graph follows
+// the routing of every replay. A token's k experts are distinct, so with T
+// decode tokens no expert holds more than T rows; the host passes that
+// bound as max_rows (1..32) and it picks the M-tile the way M does above.
+//
+// The three kernels below are the three kernels above with that prologue,
+// the per-lane A-row pointer going through a_rows, C rows offset by lo and
+// no residual epilogue (the MoE output goes through combine). They are
+// separate templates, not a shared __device__ body, so that the existing
+// instantiations keep their generated code (the decode step's timings in
+// profiles/r02_skinny_gemm.md are theirs). K split, LDS staging, MFMA
+// sequence and reduction order are copied line for line: the rows of expert
+// e are the bits kf_skinny_gemm / kf_skinny_gemm_q8 give for the same rows
+// and w_bank[e].
+//
+// Memory safety, not validation (as seq_lens in attention_d64.hip): m is
+// clamped into [0, min(max_rows, total_rows)], lo into [0, total_rows - m]
+// and every a_rows entry into [0, a_nrows), so no content of offsets or
+// a_rows can cause an out-of-range access; wrong offsets give wrong rows.
+
+struct kf_sk_group {
+  int lo, m;
+};
+
+__device__ __forceinline__ kf_sk_group kf_sk_group_range(
+    const int* __restrict__ offsets, int e, int max_rows, int total_rows) {
+  kf_sk_group g;
+  const int lo = offsets[e];
+  const int cap = max_rows < total_rows ? max_rows : total_rows;
+  // 64-bit difference: offsets[e+1] - lo cannot wrap for garbage offsets
+  const int64_t d = (int64_t)offsets[e + 1] - lo;
+  g.m = d < 0 ? 0 : (d > cap ? cap : (int)d);
+  g.lo = lo < 0 ? 0 : (lo > total_rows - g.m ? total_rows - g.m : lo);
+  return g;
+}
+
+// A row (in a) of permuted row r; r < total_rows
+__device__ __forceinline__ int64_t kf_sk_a_row(const int* __restrict__ a_rows,
+                                               int r, int a_nrows) {
+  if (!a_rows) return r;
+  const int s = a_rows[r];
+  return s < 0 ? 0 : (s >= a_nrows ? a_nrows - 1 : s);
+}
+
+template <int SKW>
+__global__ __launch_bounds__(SKW * 64, 2) void kf_skinny_gemm_grouped_kernel(
+    unsigned short* __restrict__ c, const unsigned short* __restrict__ a,
+    const unsigned short* __restrict__ w_bank,
+    const int* __restrict__ offsets, const int* __restrict__ a_rows,
+    int max_rows, int total_rows, int a_nrows, int64_t N, int64_t K) {
+  __shared__ float red[SKW][SK_NT][SK_NT];
+
+  const kf_sk_group g =
+      kf_sk_group_range(offsets, blockIdx.y, max_rows, total_rows);
+  // an expert without rows leaves before any load of W: decode is
+  // weight-bandwidth-bound, and the unrouted experts' banks staying in HBM
+  // is the whole saving over running every expert on every token
+  if (g.m == 0) return;
+  const int M = g.m;
+  const unsigned short* w = w_bank + (int64_t)blockIdx.y * N * K;
+
+  const int64_t n0 = (int64_t)blockIdx.x * SK_NT;
+  const int tid = threadIdx.x;
+  const int wv = tid / KF_WAVE;
+  const int lane = tid & (KF_WAVE - 1);
+  const int l15 = lane & 15;
+  const int hi4 = lane >> 4;
+
+  kf_f32x4s acc = kf_f32x4s{0.f, 0.f, 0.f, 0.f};
+  const unsigned short* wrow = w + (n0 + l15) * K;
+  const bool arow_ok = l15 < M;
+  const unsigned short* arow =
+      a + kf_sk_a_row(a_rows, g.lo + (arow_ok ? l15 : 0), a_nrows) * K;
+  const kf_bf16x8s zero8 = kf_bf16x8s{0, 0, 0, 0, 0, 0, 0, 0};
+  const int64_t step = (int64_t)SKW * 32;
+  int64_t k = (int64_t)wv * 32;
+  for (; k + 7 * step + 32 <= K; k += 8 * step) {
+    kf_bf16x8s afs[8], wfs[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int64_t ku = k + u * step + hi4 * 8;
+      afs[u] = arow_ok
+          ? *reinterpret_cast<const kf_bf16x8s*>(arow + ku) : zero8;
+      wfs[u] = *reinterpret_cast<const kf_bf16x8s*>(wrow + ku);
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afs[u], wfs[u], acc,
+                                                    0, 0, 0);
+  }
+  for (; k < K; k += step) {
+    kf_bf16x8s af = arow_ok
+        ? *reinterpret_cast<const kf_bf16x8s*>(arow + k + hi4 * 8)
+        : zero8;
+    kf_bf16x8s wf =
+        *reinterpret_cast<const kf_bf16x8s*>(wrow + k + hi4 * 8);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, wf, acc, 0, 0, 0);
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) red[wv][hi4 * 4 + j][l15] = acc[j];
+  __syncthreads();
+  if (tid < SK_NT * SK_NT) {
+    const int row = tid / SK_NT, col = tid % SK_NT;
+    if (row < M && n0 + col < N) {
+      float s = 0.f;
+#pragma unroll
+      for (int ww = 0; ww < SKW; ++ww) s += red[ww][row][col];
+      c[(int64_t)(g.lo + row) * N + n0 + col] = kf_f32_to_bf16(s);
+    }
+  }
+}
+
+template <int MT>
+__global__ __launch_bounds__(SKL_W * 64, 2) void kf_skinny_lds_grouped_kernel(
+    unsigned short* __restrict__ c, const unsigned short* __restrict__ a,
+    const unsigned short* __restrict__ w_bank,
+    const int* __restrict__ offsets, const int* __restrict__ a_rows,
+    int max_rows, int total_rows, int a_nrows, int64_t N, int64_t K) {
+  __shared__ unsigned short wbuf[2][SK_NT][SKL_STRIDE];
+  __shared__ float red[SKL_W][MT][SK_NT];
+
+  const kf_sk_group g =
+      kf_sk_group_range(offsets, blockIdx.y, max_rows, total_rows);
+  if (g.m == 0) return;  // before any load of W (see the direct kernel)
+  const int M = g.m;
+  const unsigned short* w = w_bank + (int64_t)blockIdx.y * N * K;
+
+  const int64_t n0 = (int64_t)blockIdx.x * SK_NT;
+  const int tid = threadIdx.x;
+  const int wv = tid / KF_WAVE;
+  const int lane = tid & (KF_WAVE - 1);
+  const int l15 = lane & 15;
+  const int hi4 = lane >> 4;
+
+  const int NMT = MT / 16;
+  kf_f32x4s acc[NMT];
+  bool arow_ok[NMT];
+  const unsigned short* arow[NMT];
+#pragma unroll
+  for (int t = 0; t < NMT; ++t) {
+    acc[t] = kf_f32x4s{0.f, 0.f, 0.f, 0.f};
+    arow_ok[t] = l15 + 16 * t < M;
+    arow[t] = a + kf_sk_a_row(a_rows,
+                              g.lo + (arow_ok[t] ? l15 + 16 * t : 0),
+                              a_nrows) * K;
+  }
+  const kf_bf16x8s zero8 = kf_bf16x8s{0, 0, 0, 0, 0, 0, 0, 0};
+  const unsigned short* wr0 = w + (n0 + 2 * wv) * K + lane * 8;
+  const unsigned short* wr1 = wr0 + K;
+
+  const int64_t nch = K / SKL_KC;
+  const int ke0 = wv * 64 + hi4 * 8;
+  kf_bf16x8s st0 = *reinterpret_cast<const kf_bf16x8s*>(wr0);
+  kf_bf16x8s st1 = *reinterpret_cast<const kf_bf16x8s*>(wr1);
+  kf_bf16x8s af0[NMT], af1[NMT];
+#pragma unroll
+  for (int t = 0; t < NMT; ++t) {
+    af0[t] = arow_ok[t]
+        ? *reinterpret_cast<const kf_bf16x8s*>(arow[t] + ke0) : zero8;
+    af1[t] = arow_ok[t]
+        ? *reinterpret_cast<const kf_bf16x8s*>(arow[t] + ke0 + 32) : zero8;
+  }
+  *reinterpret_cast<kf_bf16x8s*>(&wbuf[0][2 * wv][lane * 8]) = st0;
+  *reinterpret_cast<kf_bf16x8s*>(&wbuf[0][2 * wv + 1][lane * 8]) = st1;
+  for (int64_t ch = 0; ch < nch; ++ch) {
+    kf_bf16x8s a0[NMT], a1[NMT];
+#pragma unroll
+    for (int t = 0; t < NMT; ++t) {
+      a0[t] = af0[t];
+      a1[t] = af1[t];
+    }
+    if (ch + 1 < nch) {
+      st0 = *reinterpret_cast<const kf_bf16x8s*>(wr0 + (ch + 1) * SKL_KC);
+      st1 = *reinterpret_cast<const kf_bf16x8s*>(wr1 + (ch + 1) * SKL_KC);
+#pragma unroll
+      for (int t = 0; t < NMT; ++t)
+        if (arow_ok[t]) {
+          af0[t] = *reinterpret_cast<const kf_bf16x8s*>(
+              arow[t] + (ch + 1) * SKL_KC + ke0);
+          af1[t] = *reinterpret_cast<const kf_bf16x8s*>(
+              arow[t] + (ch + 1) * SKL_KC + ke0 + 32);
+        }
+    }
+    __syncthreads();
+    kf_bf16x8s wf0 =
+        *reinterpret_cast<const kf_bf16x8s*>(&wbuf[ch & 1][l15][ke0]);
+    kf_bf16x8s wf1 =
+        *reinterpret_cast<const kf_bf16x8s*>(&wbuf[ch & 1][l15][ke0 + 32]);
+#pragma unroll
+    for (int t = 0; t < NMT; ++t) {
+      acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0[t], wf0, acc[t],
+                                                       0, 0, 0);
+      acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1[t], wf1, acc[t],
+                                                       0, 0, 0);
+    }
+    if (ch + 1 < nch) {
+      const int b = (int)((ch + 1) & 1);
+      *reinterpret_cast<kf_bf16x8s*>(&wbuf[b][2 * wv][lane * 8]) = st0;
+      *reinterpret_cast<kf_bf16x8s*>(&wbuf[b][2 * wv + 1][lane * 8]) = st1;
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < NMT; ++t)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      red[wv][16 * t + hi4 * 4 + j][l15] = acc[t][j];
+  __syncthreads();
+  if (tid < MT * SK_NT) {
+    const int row = tid / SK_NT, col = tid % SK_NT;
+    if (row < M && n0 + col < N) {
+      float s = 0.f;
+#pragma unroll
+      for (int ww = 0; ww < SKL_W; ++ww) s += red[ww][row][col];
+      c[(int64_t)(g.lo + row) * N + n0 + col] = kf_f32_to_bf16(s);
+    }
+  }
+}
+
+// w8 is the bank flattened to [n_groups * N, K] fp8 rows, one fp32 scale per
+// row: expert e, column n uses wscale[e * N + n]
+template <int MT>
+__global__ __launch_bounds__(SKL_W * 64, 2) void kf_skinny_q8_grouped_kernel(
+    unsigned short* __restrict__ c, const unsigned short* __restrict__ a,
+    const unsigned char* __restrict__ w8_bank,
+    const float* __restrict__ wscale_bank, const int* __restrict__ offsets,
+    const int* __restrict__ a_rows, int max_rows, int total_rows,
+    int a_nrows, int64_t N, int64_t K) {
+  __shared__ unsigned char wbuf8[2][SK_NT][SKQ_STRIDE];
+  __shared__ float red[SKL_W][MT][SK_NT];
+
+  const kf_sk_group g =
+      kf_sk_group_range(offsets, blockIdx.y, max_rows, total_rows);
+  if (g.m == 0) return;  // before any load of W (see the direct kernel)
+  const int M = g.m;
+  const unsigned char* w8 = w8_bank + (int64_t)blockIdx.y * N * K;
+  const float* wscale = wscale_bank + (int64_t)blockIdx.y * N;
+
+  const int64_t n0 = (int64_t)blockIdx.x * SK_NT;
+  const int tid = threadIdx.x;
+  const int wv = tid / KF_WAVE;
+  const int lane = tid & (KF_WAVE - 1);
+  const int l15 = lane & 15;
+  const int hi4 = lane >> 4;
+
+  const int NMT = MT / 16;
+  kf_f32x4s acc[NMT];
+  bool arow_ok[NMT];
+  const unsigned short* arow[NMT];
+#pragma unroll
+  for (int t = 0; t < NMT; ++t) {
+    acc[t] = kf_f32x4s{0.f, 0.f, 0.f, 0.f};
+    arow_ok[t] = l15 + 16 * t < M;
+    arow[t] = a + kf_sk_a_row(a_rows,
+                              g.lo + (arow_ok[t] ? l15 + 16 * t : 0),
+                              a_nrows) * K;
+  }
+  const kf_bf16x8s zero8 = kf_bf16x8s{0, 0, 0, 0, 0, 0, 0, 0};
+  typedef unsigned int kf_u32x4q __attribute__((ext_vector_type(4)));
+  const unsigned char* wr0 = w8 + (n0 + 2 * wv) * K + lane * 16;
+  const unsigned char* wr1 = wr0 + K;
+
+  const int64_t nch = K / SKQ_KC;
+  const int ke0 = wv * 128 + hi4 * 8;
+  kf_u32x4q st0 = *reinterpret_cast<const kf_u32x4q*>(wr0);
+  kf_u32x4q st1 = *reinterpret_cast<const kf_u32x4q*>(wr1);
+  kf_bf16x8s af[4][NMT];
+#pragma unroll
+  for (int si = 0; si < 4; ++si)
+#pragma unroll
+    for (int t = 0; t < NMT; ++t)
+      af[si][t] = arow_ok[t]
+          ? *reinterpret_cast<const kf_bf16x8s*>(arow[t] + ke0 + 32 * si)
+          : zero8;
+  *reinterpret_cast<kf_u32x4q*>(&wbuf8[0][2 * wv][lane * 16]) = st0;
+  *reinterpret_cast<kf_u32x4q*>(&wbuf8[0][2 * wv + 1][lane * 16]) = st1;
+  for (int64_t ch = 0; ch < nch; ++ch) {
+    kf_bf16x8s acur[4][NMT];
+#pragma unroll
+    for (int si = 0; si < 4; ++si)
+#pragma unroll
+      for (int t = 0; t < NMT; ++t) acur[si][t] = af[si][t];
+    if (ch + 1 < nch) {
+      st0 = *reinterpret_cast<const kf_u32x4q*>(wr0 + (ch + 1) * SKQ_KC);
+      st1 = *reinterpret_cast<const kf_u32x4q*>(wr1 + (ch + 1) * SKQ_KC);
+#pragma unroll
+      for (int si = 0; si < 4; ++si)
+#pragma unroll
+        for (int t = 0; t < NMT; ++t)
+          if (arow_ok[t])
+            af[si][t] = *reinterpret_cast<const kf_bf16x8s*>(
+                arow[t] + (ch + 1) * SKQ_KC + ke0 + 32 * si);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int si = 0; si < 4; ++si) {
+      kf_bf16x8s wf =
+          kf_fp8x8_to_bf16x8(&wbuf8[ch & 1][l15][ke0 + 32 * si]);
+#pragma unroll
+      for (int t = 0; t < NMT; ++t)
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(acur[si][t], wf,
+                                                         acc[t], 0, 0, 0);
+    }
+    if (ch + 1 < nch) {
+      const int b = (int)((ch + 1) & 1);
+      *reinterpret_cast<kf_u32x4q*>(&wbuf8[b][2 * wv][lane * 16]) = st0;
+      *reinterpret_cast<kf_u32x4q*>(&wbuf8[b][2 * wv + 1][lane * 16]) =
+          st1;
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < NMT; ++t)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      red[wv][16 * t + hi4 * 4 + j][l15] = acc[t][j];
+  __syncthreads();
+  if (tid < MT * SK_NT) {
+    const int row = tid / SK_NT, col = tid % SK_NT;
+    if (row < M && n0 + col < N) {
+      float s = 0.f;
+#pragma unroll
+      for (int ww = 0; ww < SKL_W; ++ww) s += red[ww][row][col];
+      s *= wscale[n0 + col];
+      c[(int64_t)(g.lo + row) * N + n0 + col] = kf_f32_to_bf16(s);
+    }
+  }
+}
+
+// shape limits shared by the two grouped entry points; the row counts are
+// int32 in the kernels
+static bool kf_sk_grouped_ok(int64_t n_groups, int64_t max_rows,
+                             int64_t total_rows, int64_t a_nrows, int64_t N) {
+  return n_groups >= 1 && n_groups <= 65535 && max_rows >= 1 &&
+         max_rows <= 32 && total_rows >= 0 && total_rows < INT32_MAX &&
+         a_nrows >= 1 && a_nrows < INT32_MAX && N >= SK_NT && N % SK_NT == 0 &&
+         N / SK_NT < INT32_MAX;
+}
+
+// c [total_rows, N], a [a_nrows, K] (a_rows null: a_nrows == total_rows),
+// w_bank [n_groups, N, K], all contiguous bf16; offsets int32 [n_groups + 1],
+// a_rows nullable int32 [total_rows]; both device arrays.
+KF_EXPORT int kf_skinny_gemm_grouped(void* c, const void* a,
+                                     const void* w_bank, const int* offsets,
+                                     const int* a_rows, int64_t n_groups,
+                                     int64_t max_rows, int64_t total_rows,
+                                     int64_t a_nrows, int64_t N, int64_t K,
+                                     void* stream) {
+  if (!kf_sk_grouped_ok(n_groups, max_rows, total_rows, a_nrows, N) ||
+      K < 32 || K % 32 || (!a_rows && a_nrows < total_rows))
+    return (int)hipErrorInvalidValue;
+  const bool lds_ok = K % SKL_KC == 0;
+  if (max_rows > 16 && !lds_ok) return (int)hipErrorInvalidValue;
+  if (total_rows == 0) return 0;
+  dim3 grid((unsigned)(N / SK_NT), (unsigned)n_groups, 1);
+#define KF_SKG_LAUNCH(KERNEL, THREADS)                                     \
+  hipLaunchKernelGGL(KERNEL, grid, dim3(THREADS), 0, (hipStream_t)stream,  \
+                     (unsigned short*)c, (const unsigned short*)a,         \
+                     (const unsigned short*)w_bank, offsets, a_rows,       \
+                     (int)max_rows, (int)total_rows, (int)a_nrows, N, K)
+  if (lds_ok && max_rows > 16)
+    KF_SKG_LAUNCH(kf_skinny_lds_grouped_kernel<32>, SKL_W * 64);
+  else if (lds_ok)
+    KF_SKG_LAUNCH(kf_skinny_lds_grouped_kernel<16>, SKL_W * 64);
+  else if (N / SK_NT < 512)  // the direct kernels, chosen as kf_skinny_gemm does
+    KF_SKG_LAUNCH(kf_skinny_gemm_grouped_kernel<8>, 8 * 64);
+  else
+    KF_SKG_LAUNCH(kf_skinny_gemm_grouped_kernel<4>, 4 * 64);
+  return (int)hipGetLastError();
+}
+
+// as above with w8 [n_groups * N, K] e4m3 and wscale fp32 [n_groups * N]
+KF_EXPORT int kf_skinny_gemm_grouped_q8(void* c, const void* a,
+                                        const void* w8, const float* wscale,
+                                        const int* offsets, const int* a_rows,
+                                        int64_t n_groups, int64_t max_rows,
+                                        int64_t total_rows, int64_t a_nrows,
+                                        int64_t N, int64_t K, void* stream) {
+  if (!kf_sk_grouped_ok(n_groups, max_rows, total_rows, a_nrows, N) ||
+      K < SKQ_KC || K % SKQ_KC || (!a_rows && a_nrows < total_rows))
+    return (int)hipErrorInvalidValue;
+  if (total_rows == 0) return 0;
+  dim3 grid((unsigned)(N / SK_NT), (unsigned)n_groups, 1);
+#define KF_SKGQ_LAUNCH(MT)                                                   \
+  hipLaunchKernelGGL(kf_skinny_q8_grouped_kernel<MT>, grid,                  \
+                     dim3(SKL_W * 64), 0, (hipStream_t)stream,               \
+                     (unsigned short*)c, (const unsigned short*)a,           \
+                     (const unsigned char*)w8, wscale, offsets, a_rows,      \
+                     (int)max_rows, (int)total_rows, (int)a_nrows, N, K)
+  if (max_rows > 16) KF_SKGQ_LAUNCH(32);
+  else KF_SKGQ_LAUNCH(16);
+  return (int)hipGetLastError();
+}

@@ -212,3 +212,24 @@ def moe_combine_bwd(dout: torch.Tensor, y: torch.Tensor, topw: torch.Tensor,
         dy[p[sel]] = (topw[sel, s:s + 1].float() * d32[sel]).to(y.dtype)
         dw[sel, s] = (d32[sel] * y[p[sel]].float()).sum(dim=-1)
     return dy, dw.to(topw.dtype)
+
+
+def grouped_linear_offsets(x: torch.Tensor, w_bank: torch.Tensor,
+                           offsets: torch.Tensor, rows=None) -> torch.Tensor:
+    """The reference of ops.grouped_skinny_linear: w_bank [n, N, K], offsets
+    [n + 1] as a tensor (read on the host here: not a capture path) ->
+    y [R, N], y[lo_e + i] = x[rows[lo_e + i] if rows is given else lo_e + i]
+    @ w_bank[e].T, R = rows.numel() or x.shape[0]. Rows no expert owns are
+    zeros. One torch.mm per expert that has rows, over the same slices as
+    ops.grouped_linear, so the two agree bit for bit on the CPU."""
+    n, N, _ = w_bank.shape
+    total = x.shape[0] if rows is None else rows.numel()
+    y = torch.zeros(total, N, dtype=x.dtype, device=x.device)
+    off = offsets.tolist()
+    for e in range(n):
+        lo, hi = off[e], off[e + 1]
+        if hi <= lo:
+            continue
+        xs = x[lo:hi] if rows is None else x[rows[lo:hi].long()]
+        torch.mm(xs, w_bank[e].t(), out=y[lo:hi])
+    return y

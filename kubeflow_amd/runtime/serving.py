@@ -17,6 +17,7 @@ the training flash-attention kernel over the padded prompt.
 """
 from __future__ import annotations
 
+import logging
 import os
 import queue
 import threading
@@ -86,6 +87,30 @@ class Request:
     error: str = ""
 
 
+def moe_decode_mode() -> str:
+    """KF_MOE_DECODE: how the decode step runs an MoE block. "routed" (the
+    default: 3-5x faster per block at batch 1-32, docs/KERNELS.md) is
+    MoEMLP.decode_routed, the grouped skinny GEMM over device offsets, which
+    itself falls back to dense where it does not apply (the CPU, shapes the
+    kernels reject); "dense" is MoEMLP.decode_dense, every expert on every
+    token."""
+    mode = os.environ.get("KF_MOE_DECODE", "routed")
+    if mode not in ("routed", "dense"):
+        raise ValueError(f"KF_MOE_DECODE must be 'routed' or 'dense', got "
+                         f"{mode!r}")
+    return mode
+
+
+def quantize_moe_banks(moe):
+    """((w13_8, w13_scale), (w2_8, w2_scale)): the two expert banks of an
+    MoEMLP through ops.quantize_fp8_rows on their flattened [E * out, in]
+    views, one scale per (expert, output row), as
+    ops.moe_experts_decode(q8=...) takes them."""
+    return tuple(
+        ops.quantize_fp8_rows(w.reshape(-1, w.shape[-1]))
+        for w in (moe.experts_w13, moe.experts_w2))
+
+
 class InferenceEngine:
     def __init__(self, model_name: str, device=None, max_slots: int = 32,
                  smax: int = 4096, max_batch: int = 32,
@@ -147,17 +172,29 @@ class InferenceEngine:
                              "(supported: fp8)")
         self.quant = quant == "fp8"
         self._qw = None
-        if self.quant and not getattr(cfg, "n_experts", 0):
+        moe = bool(getattr(cfg, "n_experts", 0))
+        if self.quant and moe and not self._moe_q8_usable(max_batch):
+            # the dense MoE decode has no fp8 experts: as before, such a
+            # model serves bf16 weights throughout
+            logging.getLogger(__name__).warning(
+                "KF_SERVE_QUANT=fp8 is off for %s: its experts need the "
+                "routed decode path (KF_MOE_DECODE) on a GPU, max_batch <= 32 "
+                "and hidden and ffn sizes that are multiples of 1024 (the "
+                "routed fp8 kernel's shapes)", cfg.name)
+            self.quant = False
+        if self.quant:
+            names = ("wqkv", "wo") if moe else ("wqkv", "wo", "w13", "w2")
             self._qw = [
                 {n: ops.quantize_fp8_rows(getattr(layer, n).weight)
-                 for n in ("wqkv", "wo", "w13", "w2")}
+                 for n in names}
                 for layer in self.model.layers
             ]
+            if moe:
+                for qw, layer in zip(self._qw, self.model.layers):
+                    qw["moe"] = quantize_moe_banks(layer.moe)
             # lm_head stays bf16 under "small" routing (sampling
             # sensitivity); KF_SKINNY=all opts it into fp8 too
             self._q_lm = ops.quantize_fp8_rows(self.model.lm_head.weight)
-        elif self.quant:
-            self.quant = False  # MoE decode is eager/dense — not routed
         smax = min(smax, cfg.max_seq_len)
         self.cache = KVCache(cfg.n_layers, max_slots, smax,
                              cfg.n_kv_heads, cfg.head_dim, self.device, dtype)
@@ -179,12 +216,26 @@ class InferenceEngine:
         # bucket (the ~10 kernels x 32 layers of launch overhead dominate
         # small-batch decode latency otherwise). One cache slot is reserved
         # as the padding target for bucket rows beyond the live batch.
-        # MoE decode goes through MoEMLP.decode_dense (all experts on all
-        # tokens, dense gate mask) — fixed shapes, so it captures.
+        # MoE decode goes through MoEMLP.decode_routed (expert offsets stay
+        # on the device) or, under KF_MOE_DECODE=dense, MoEMLP.decode_dense
+        # (all experts on all tokens, dense gate mask) — fixed shapes and no
+        # host sync either way, so both capture.
         self.use_graphs = (self.device.type == "cuda"
                            and os.environ.get("KF_SERVE_GRAPH", "1") == "1")
         self._graphs = {}
         self._pad_slot = self.cache.alloc() if self.use_graphs else None
+
+    def _moe_q8_usable(self, max_batch: int) -> bool:
+        """fp8 experts exist only on the routed decode path: KF_MOE_DECODE
+        must select it and every layer must take it at the largest decode
+        batch (the smaller buckets then qualify too)."""
+        if moe_decode_mode() != "routed":
+            return False
+        cfg = self.model.cfg
+        probe = torch.empty(max_batch, 1, cfg.hidden_size, device=self.device,
+                            dtype=self.model.embed.weight.dtype)
+        return all(layer.moe.routed_decode_ok(probe, q8=True)
+                   for layer in self.model.layers)
 
     # ------------------------------------------------------------- public
     def start(self, precapture: bool | None = None):
@@ -645,6 +696,7 @@ class InferenceEngine:
                "all": {"qkv", "wo", "w13", "w2", "lm"}}.get(
                    mode, set(mode.split(",")))
         qw = self._qw if self.quant else None
+        moe_routed = moe_decode_mode() == "routed"
 
         def _lin(name, wname):
             if qw is not None and name in sel:
@@ -690,7 +742,12 @@ class InferenceEngine:
             x = lin_wo(li, o.reshape(N, 1, cfg.n_heads * cfg.head_dim),
                        layer.wo.weight, x)  # residual fused in epilogue
             if layer.moe is not None:
-                x = x + layer.moe.decode_dense(layer.mlp_norm(x))
+                if moe_routed:
+                    x = x + layer.moe.decode_routed(
+                        layer.mlp_norm(x),
+                        q8=qw[li]["moe"] if qw is not None else None)
+                else:
+                    x = x + layer.moe.decode_dense(layer.mlp_norm(x))
             else:
                 # NOTE: fusing swiglu into the w2 fragment loader
                 # measured WORSE (replay 4.3 -> 5.0, quant 3.5 -> 4.6):
