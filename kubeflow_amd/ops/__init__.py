@@ -279,23 +279,29 @@ def kv_store(cache_k: torch.Tensor, cache_v: torch.Tensor,
     cache_v[slots.long(), positions] = v.reshape(n, *cache_v.shape[2:])
 
 
-def skinny_linear(x: torch.Tensor, weight: torch.Tensor,
-                  residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Decode-batch linear y = x @ W^T (+ residual) for small leading dims
-    (M <= 32): the LDS-staged weight-streaming kernel (skinny_gemm.hip)
-    replaces hipBLASLt's ~30-50%-of-BW GEMV path in the serving decode
-    step; `residual` fuses the following elementwise add into the
-    epilogue. Falls back to F.linear off-GPU or for larger M /
-    unsupported shapes. Inference-only (no autograd)."""
+def _skinny_shape_ok(rows: int, N: int, K: int, q8: bool) -> bool:
+    """The shape rule of skinny_gemm.hip for `rows` batch rows against
+    [N, K] weights: the LDS kernel takes K % 512 == 0 (q8: K % 1024 == 0)
+    up to 32 rows, the direct bf16 kernel K % 32 == 0 up to 16 rows."""
+    if not 1 <= rows <= 32 or N % 16:
+        return False
+    if q8:
+        return K % 1024 == 0
+    return K % 512 == 0 or (K % 32 == 0 and rows <= 16)
+
+
+def _skinny(x, w, scale, residual):
+    """Shared body of the two skinny linears; scale None = bf16 weight."""
     shape = x.shape
     M = 1
     for d in shape[:-1]:
         M *= int(d)
     K = shape[-1]
-    N = weight.shape[0]
-    if (not _use_native(x) or M > 32 or K % 32 or N % 16
-            or x.dtype != torch.bfloat16 or (M > 16 and K % 512)):
-        y = torch.nn.functional.linear(x, weight)
+    N = w.shape[0]
+    if (not _use_native(x) or x.dtype != torch.bfloat16
+            or not _skinny_shape_ok(M, N, K, scale is not None)):
+        wb = w if scale is None else dequantize_fp8_rows(w, scale, x.dtype)
+        y = torch.nn.functional.linear(x, wb)
         return y + residual if residual is not None else y
     lib = _backend.require()
     x2 = x.reshape(M, K)
@@ -307,11 +313,28 @@ def skinny_linear(x: torch.Tensor, weight: torch.Tensor,
         if not r2.is_contiguous():
             r2 = r2.contiguous()
     y = torch.empty(M, N, dtype=x.dtype, device=x.device)
-    _backend.check(
-        lib.kf_skinny_gemm(_p(y), _p(x2), _p(weight), _p(r2), M, N, K,
-                           K, 0, 0, _stream()),
-        "skinny_gemm")
+    if scale is None:
+        _backend.check(
+            lib.kf_skinny_gemm(_p(y), _p(x2), _p(w), _p(r2), M, N, K,
+                               K, 0, 0, _stream()),
+            "skinny_gemm")
+    else:
+        _backend.check(
+            lib.kf_skinny_gemm_q8(_p(y), _p(x2), _p(w), _fp(scale), _p(r2),
+                                  M, N, K, K, 0, 0, _stream()),
+            "skinny_gemm_q8")
     return y.view(*shape[:-1], N)
+
+
+def skinny_linear(x: torch.Tensor, weight: torch.Tensor,
+                  residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Decode-batch linear y = x @ W^T (+ residual) for small leading dims
+    (M <= 32): the LDS-staged weight-streaming kernel (skinny_gemm.hip)
+    replaces hipBLASLt's ~30-50%-of-BW GEMV path in the serving decode
+    step; `residual` fuses the following elementwise add into the
+    epilogue. Falls back to F.linear off-GPU or for larger M /
+    unsupported shapes. Inference-only (no autograd)."""
+    return _skinny(x, weight, None, residual)
 
 
 def quantize_fp8_rows(w: torch.Tensor):
@@ -341,32 +364,7 @@ def skinny_linear_q8(x: torch.Tensor, w8: torch.Tensor,
     weights halve the HBM traffic of the weight-BW-bound decode GEMMs
     (skinny_gemm.hip kf_skinny_q8_kernel); activations stay bf16 and the
     MFMA runs bf16 (W8A16). Serving-only, behind KF_SERVE_QUANT=fp8."""
-    shape = x.shape
-    M = 1
-    for d in shape[:-1]:
-        M *= int(d)
-    K = shape[-1]
-    N = w8.shape[0]
-    if (not _use_native(x) or M > 32 or K % 1024 or N % 16
-            or x.dtype != torch.bfloat16):
-        y = torch.nn.functional.linear(
-            x, dequantize_fp8_rows(w8, scale, x.dtype))
-        return y + residual if residual is not None else y
-    lib = _backend.require()
-    x2 = x.reshape(M, K)
-    if not x2.is_contiguous():
-        x2 = x2.contiguous()
-    r2 = None
-    if residual is not None:
-        r2 = residual.reshape(M, N)
-        if not r2.is_contiguous():
-            r2 = r2.contiguous()
-    y = torch.empty(M, N, dtype=x.dtype, device=x.device)
-    _backend.check(
-        lib.kf_skinny_gemm_q8(_p(y), _p(x2), _p(w8), _fp(scale), _p(r2),
-                              M, N, K, K, 0, 0, _stream()),
-        "skinny_gemm_q8")
-    return y.view(*shape[:-1], N)
+    return _skinny(x, w8, scale, residual)
 
 
 def decode_rope_store(qkv: torch.Tensor, cache_k: torch.Tensor,
@@ -1567,12 +1565,8 @@ def grouped_skinny_ok(T: int, N: int, K: int, dtype,
     captures a graph, since the fallback of grouped_skinny_linear syncs. The
     LDS kernel needs K % 512 == 0 (q8: K % 1024 == 0) and T <= 32, the direct
     bf16 kernel K % 32 == 0 and T <= 16."""
-    if (dtype != torch.bfloat16 or not 1 <= T <= GROUPED_SKINNY_MAX_ROWS
-            or N < 16 or N % 16 or K < 32):
-        return False
-    if q8:
-        return K % 1024 == 0
-    return K % 512 == 0 or (K % 32 == 0 and T <= 16)
+    return (dtype == torch.bfloat16 and N >= 16 and K >= 32
+            and _skinny_shape_ok(T, N, K, q8))
 
 
 def _grouped_skinny(x, w, scale, offsets, max_rows, rows, out, n, N, K):

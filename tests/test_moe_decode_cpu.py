@@ -50,6 +50,30 @@ def test_grouped_skinny_ok_follows_the_kernels_shape_rules():
     assert not ops.grouped_skinny_ok(4, 1024, 512, bf, q8=True)
 
 
+# (rows, N, K, q8, accepted), from the "Shapes" rule of docs/KERNELS.md: LDS
+# kernel K % 512 (q8: K % 1024) up to 32 rows, direct kernel K % 32 up to 16
+# rows, N % 16, at least one row
+SHAPE_RULE = [
+    (0, 64, 512, False, False), (1, 64, 512, False, True),
+    (16, 64, 512, False, True), (17, 64, 512, False, True),
+    (32, 64, 512, False, True), (33, 64, 512, False, False),
+    (16, 64, 96, False, True), (17, 64, 96, False, False),
+    (4, 64, 40, False, False), (4, 24, 512, False, False),
+    (4, 64, 512, True, False), (4, 64, 1024, True, True),
+]
+
+
+@pytest.mark.parametrize("rows,N,K,q8,accepted", SHAPE_RULE)
+def test_skinny_shape_rule_is_one_predicate(rows, N, K, q8, accepted):
+    """The rule skinny_linear, skinny_linear_q8 and grouped_skinny_ok share."""
+    assert ops._skinny_shape_ok(rows, N, K, q8) is accepted
+    assert ops.grouped_skinny_ok(rows, N, K, torch.bfloat16, q8=q8) is accepted
+    # what grouped_skinny_ok asks on top: no empty dimension, bf16 only
+    assert ops.grouped_skinny_ok(rows, 0, K, torch.bfloat16, q8=q8) is False
+    assert ops.grouped_skinny_ok(rows, N, 0, torch.bfloat16, q8=q8) is False
+    assert ops.grouped_skinny_ok(rows, N, K, torch.float16, q8=q8) is False
+
+
 def test_reference_grouped_linear_empty_and_full_experts():
     g = _gen(3)
     x = torch.randn(6, 16, generator=g)

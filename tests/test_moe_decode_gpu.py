@@ -12,6 +12,8 @@ top. Shapes are the smallest that enter each loop of each kernel:
                  q8: K = 1024 (one) and 2048 (two)
   direct <8>     K = 96 (tail loop only), 2080 (one pass of the 8-deep
                  unrolled loop, then the tail)
+  direct <4>     N = 8192 (N/16 = 512 blocks), K = 1056: one pass of the
+                 8-deep loop, then a tail step in wave 0 only; one pattern
   N = 32 and 48: two and three 16-column blocks per expert
   max_rows <= 16 and 17..32: the two M-tile templates.
 """
@@ -127,9 +129,15 @@ def test_grouped_lds_kernel_matches_skinny_linear_bits(K, N, pat):
     _check_grouped(N, K, pat[0], pat[1], q8=False)
 
 
-@pytest.mark.parametrize("pat", SMALL, ids=SMALL_IDS)
-@pytest.mark.parametrize("N", [32, 48])
-@pytest.mark.parametrize("K", [96, 2080])
+# every small pattern at the <8> shapes, one at the <4> shape; the ids are
+# those of the stacked pat / N / K parametrisation this list replaces
+DIRECT = [(K, N, p, i) for K in (96, 2080) for N in (32, 48)
+          for p, i in zip(SMALL, SMALL_IDS)]
+DIRECT.append((1056, 8192, SMALL[0], SMALL_IDS[0]))
+
+
+@pytest.mark.parametrize("K,N,pat", [c[:3] for c in DIRECT],
+                         ids=["{0}-{1}-{3}".format(*c) for c in DIRECT])
 def test_grouped_direct_kernel_matches_skinny_linear_bits(K, N, pat):
     _check_grouped(N, K, pat[0], pat[1], q8=False)
 
