@@ -77,6 +77,30 @@ def _i32p(t):
     return ctypes.cast(t.data_ptr(), ctypes.POINTER(ctypes.c_int32))
 
 
+def _index_arg(op: str, name: str, t, dtype: torch.dtype, n: int,
+               like: torch.Tensor) -> None:
+    """The kernels read index tensors through a bare pointer at a fixed
+    width: `t` must be a contiguous `dtype` tensor of shape [n] on `like`'s
+    device, or the launch would scatter to (or read from) the wrong rows.
+    Metadata only: no host sync and no value check, so it is safe under
+    graph capture."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(
+            f"{op}: {name} must be a tensor, got {type(t).__name__}")
+    if t.dtype != dtype:
+        raise TypeError(
+            f"{op}: {name} must be {dtype} (the kernel reads it at that "
+            f"width), got {t.dtype}")
+    if t.device != like.device:
+        raise ValueError(
+            f"{op}: {name} must be on {like.device}, got {t.device}")
+    if tuple(t.shape) != (n,):
+        raise ValueError(
+            f"{op}: {name} must have shape [{n}], got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{op}: {name} must be contiguous")
+
+
 def _use_native(t: torch.Tensor) -> bool:
     if not t.is_cuda:
         return False
@@ -242,6 +266,9 @@ def rope(q: torch.Tensor, k: torch.Tensor, cos: torch.Tensor,
     """q [B,S,Hq,D], k [B,S,Hkv,D]; cos/sin fp32 [>=S+off, D/2].
     positions: optional int64 [B] per-row base position (serving decode)."""
     if _use_native(q):
+        if positions is not None:
+            _index_arg("rope", "positions", positions, torch.int64,
+                       q.shape[0], q)
         return _RopeHip.apply(q, k, cos, sin, pos_offset, positions)
     if positions is not None:
         qs = [reference.rope_apply(q[i:i+1], cos, sin, int(positions[i]))
@@ -260,11 +287,15 @@ def kv_store(cache_k: torch.Tensor, cache_v: torch.Tensor,
     [slot[i], position[i]] for each sequence i — one launch instead of two
     advanced-indexing kernels per layer (kv_store.hip). cache_k/v
     [SLOTS,SMAX,Hkv,D]; k/v [N,1,Hkv,D] (or [N,Hkv,D]); slots int32 [N];
-    positions int64 [N]. Capture-safe; no autograd (serving only)."""
+    positions int64 [N] (the kernel reads them at that width: on the native
+    path another dtype, device, length or a strided tensor raises).
+    Capture-safe; no autograd (serving only)."""
     n = k.shape[0]
     row = cache_k.shape[2] * cache_k.shape[3]
     if _use_native(k) and k.dtype == torch.bfloat16 and row % 8 == 0:
         lib = _backend.require()
+        _index_arg("kv_store", "slots", slots, torch.int32, n, k)
+        _index_arg("kv_store", "positions", positions, torch.int64, n, k)
         kk, vv = k.reshape(n, row), v.reshape(n, row)
         if not kk.is_contiguous():
             kk = kk.contiguous()
@@ -383,6 +414,9 @@ def decode_rope_store(qkv: torch.Tensor, cache_k: torch.Tensor,
     q = torch.empty(n, n_heads, D, dtype=qkv.dtype, device=qkv.device)
     if (_use_native(qkv) and qkv.dtype == torch.bfloat16 and D == 128):
         lib = _backend.require()
+        _index_arg("decode_rope_store", "slots", slots, torch.int32, n, qkv)
+        _index_arg("decode_rope_store", "positions", positions, torch.int64,
+                   n, qkv)
         q3 = qkv.reshape(n, -1)
         if not q3.is_contiguous():
             q3 = q3.contiguous()
@@ -1037,7 +1071,8 @@ def attention_decode(q: torch.Tensor, kcache: torch.Tensor,
     """Single-token GQA attention over the KV cache (no autograd — serving).
 
     q [N,Hq,D] bf16; kcache/vcache [SLOTS,SMAX,Hkv,D] bf16;
-    slots/lens int32 [N]. Returns o [N,Hq,D].
+    slots/lens int32 [N] (checked on the native path: the kernel reads them
+    at that width). Returns o [N,Hq,D].
     """
     N, Hq, D = q.shape
     Hkv = kcache.shape[2]
@@ -1045,6 +1080,8 @@ def attention_decode(q: torch.Tensor, kcache: torch.Tensor,
         scale = D ** -0.5
     if _use_native(q):
         lib = _backend.require()
+        _index_arg("attention_decode", "slots", slots, torch.int32, N, q)
+        _index_arg("attention_decode", "lens", lens, torch.int32, N, q)
         q = q.contiguous()
         out = torch.empty_like(q)
         # flash-decoding split: N*Hkv blocks alone underfill the 256-CU
@@ -1129,6 +1166,8 @@ def cross_entropy(logits: torch.Tensor, targets: torch.Tensor,
                   ignore_index: int = -100):
     """Mean CE over non-ignored rows. logits [T,V] bf16, targets [T] int64."""
     if _use_native(logits):
+        _index_arg("cross_entropy", "targets", targets, torch.int64,
+                   logits.shape[0], logits)
         inplace_ok = not logits.is_leaf and logits.is_contiguous()
         return _CrossEntropyHip.apply(logits, targets, ignore_index,
                                       inplace_ok)

@@ -41,8 +41,14 @@ __global__ __launch_bounds__(64) void kf_decode_rope_store_kernel(
     } else {
       dst = ck + (((int64_t)slots[n] * smax + pos) * Hkv + (h - Hq)) * DF_D;
     }
-    dst[d] = kf_f32_to_bf16(a * c - b * s);
-    dst[d + halfD] = kf_f32_to_bf16(b * c + a * s);
+    // One rounded product, then a fused multiply-add: the form rope.hip's
+    // a*c - b*s contracts to. Left to the compiler this kernel got two
+    // rounded products and a subtract, whose fp32 result differs in the last
+    // bit and, on about one element in 10^5, in the bf16 it rounds to, so
+    // decode wrote other k bits than prefill (ops.rope) for the same token.
+    // tests/test_decode_store_gpu.py asserts the two agree bit for bit.
+    dst[d] = kf_f32_to_bf16(__builtin_fmaf(a, c, -(b * s)));
+    dst[d + halfD] = kf_f32_to_bf16(__builtin_fmaf(b, c, a * s));
   } else {  // v head: plain copy into the cache
     unsigned short* dst =
         cv + (((int64_t)slots[n] * smax + pos) * Hkv + (h - Hq - Hkv)) * DF_D;

@@ -18,6 +18,9 @@ Per-row bounds
     softmax statistics), so a correct kernel sits below 1 x; the factor 3
     covers a different summation order. It is derived from the reference
     alone, never from a kernel's output.
+  * mask probe (mask_probe_inputs): the project's fixed 2e-2 (o) / 4e-2 (dv)
+    per row against attention_oracle on the probe inputs; a mask off by one
+    key moves a row by more than 1.
   * elementwise / row kernels (rope, norms, swiglu, CE grads, adamw p16): the
     op's whole-tensor bound from tests/test_ops_gpu.py, applied per row. A
     correctly bf16-rounded row sits at 2^-9 ~ 0.002, a wrong row near 1.
@@ -33,7 +36,8 @@ from . import reference as R
 __all__ = [
     "row_err", "col_err", "rel_err", "attention_inputs", "attention_oracle",
     "emulated", "attention_case", "attention_case_varlen", "AttnCase",
-    "rope_oracle",
+    "attention_case_rect", "mask_probe_inputs", "rope_oracle",
+    "rope_store_oracle",
     "rms_norm_oracle", "layer_norm_oracle", "swiglu_oracle",
     "cross_entropy_oracle", "adamw_oracle", "decode_oracle",
     "linear_residual_oracle", "moe_mlp_oracle", "moe_mlp_emulated",
@@ -284,6 +288,91 @@ def attention_case_varlen(B: int, S: int, Hq: int, Hkv: int,
     return _ATTN_CACHE[key]
 
 
+def attention_case_rect(B: int, C: int, Skv: int, q_offset: int, Hq: int,
+                        Hkv: int, seed: int = 1234, D: int = 128) -> AttnCase:
+    """attention_case for rectangular-causal attention (chunked prefill): C
+    query rows at global offset q_offset over Skv >= q_offset + C kv rows,
+    row i attending keys <= q_offset + i. inputs = (q [B,C,Hq,D],
+    k, v [B,Skv,Hkv,D]); oracle, emu_err and bound hold "o" (and the oracle
+    "lse" [B,Hq,C]) only: there is no backward.
+
+    The oracle is rows [q_offset, q_offset + C) of the square causal
+    attention over n = q_offset + C rows: q is embedded into a zero tensor of
+    n rows, k/v are sliced to n (keys past n are visible to no row), dout is
+    zero. The bound is ROW_BOUND_FACTOR x row_err(emulated, oracle) over the
+    C rows, from the reference alone, and must exceed 2^-9 (one bf16 ulp of
+    relative error): a case with a single visible key has no emulation error
+    and is checked by equality instead."""
+    assert Skv >= q_offset + C and C >= 1 and q_offset >= 0, \
+        (C, Skv, q_offset)
+    key = ("rect", B, C, Skv, q_offset, Hq, Hkv, D, seed)
+    if key in _ATTN_CACHE:
+        return _ATTN_CACHE[key]
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    q = torch.randn(B, C, Hq, D, generator=g).bfloat16()
+    k = torch.randn(B, Skv, Hkv, D, generator=g).bfloat16()
+    v = torch.randn(B, Skv, Hkv, D, generator=g).bfloat16()
+    n = q_offset + C
+    qn = torch.zeros(B, n, Hq, D, dtype=q.dtype)
+    qn[:, q_offset:] = q
+    dout = torch.zeros(B, n, Hq, D)
+    o, lse = attention_oracle(qn, k[:, :n], v[:, :n], dout, True)[:2]
+    eo = emulated(qn, k[:, :n], v[:, :n], dout, True)[0]
+    oracle = {"o": o[:, q_offset:].contiguous(),
+              "lse": lse[:, :, q_offset:].contiguous()}
+    emu_err = {"o": row_err(eo[:, q_offset:], oracle["o"])}
+    bound = {"o": ROW_BOUND_FACTOR * emu_err["o"]}
+    assert bound["o"] > 2.0 ** -9, (key, bound)
+    _ATTN_CACHE[key] = AttnCase((q, k, v), oracle, emu_err, bound)
+    return _ATTN_CACHE[key]
+
+
+def mask_probe_inputs(B: int, Sq: int, Skv: int, Hq: int, Hkv: int,
+                      D: int = 128, seed: int = 1234):
+    """(q [B,Sq,Hq,D], k, v [B,Skv,Hkv,D], scale): bf16 inputs that pin the
+    mask boundary of every single row. The score of key j is 8 * j for every
+    query, so each query puts all its weight but e^-8 on its LAST visible
+    key: its output row is that key's v row, and dv[j] is the sum over the
+    GQA group of the dout rows whose last visible key is j. A mask that is
+    off by one key for one row moves that row to another v row.
+
+    Construction: q and k are seeded randn x 0.1; then q[..., 0] = q[..., 1]
+    = 8, k[:, j, :, 0] = 256 * (j // 32), k[:, j, :, 1] = 8 * (j % 32) and
+    scale = 0.125, all exact in bf16 (j < 2^13), so dims 0 and 1 contribute
+    exactly 0.125 * (2048 * (j // 32) + 64 * (j % 32)) = 8 * j. The other
+    D - 2 dims add 0.125 * sum of D - 2 products of two N(0, 0.01) values:
+    std 0.014 at D = 128, under 0.25 in every case used (18 sigma), against
+    a gap of 8 between neighbouring keys. v is seeded randn.
+
+    Margins, measured from the reference alone (seed 7, Hq, Hkv = 2, 1) at
+    D = 128 rect (C, Skv, off) = (300, 1115, 815), (256, 256, 0),
+    (100, 133, 33) and at D = 64 square S = 200, with row_err against
+    attention_oracle on the probe inputs; the fixed per-row bounds are 2e-2
+    (o) and 4e-2 (dv):
+      row_err(oracle o, v[limit])             <= 5.9e-4
+      mask shifted by one key either way      >= 1.54
+      one wrong row among 100 .. 300          >= 1.23
+      dv vs group-summed dout                 <= 6.6e-4; shifted a row >= 1.58
+    (tests/test_attn_probe_cpu.py prints them and asserts a factor 10 below
+    the bounds and 1.0 above).
+
+    Not for emulated(): it rounds the scores to bf16, which destroys their
+    order at this magnitude (row_err 0.98). dq and dk are pure cancellation
+    here (rms ~3e-3 against k entries in the thousands) and lse sits near
+    8 * Skv, where an absolute 1e-2 means nothing: check o and dv only."""
+    assert Skv <= 8192, Skv   # 256 * (j // 32) stays exact in bf16
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    q = torch.randn(B, Sq, Hq, D, generator=g) * 0.1
+    k = torch.randn(B, Skv, Hkv, D, generator=g) * 0.1
+    v = torch.randn(B, Skv, Hkv, D, generator=g).bfloat16()
+    j = torch.arange(Skv)
+    q[..., 0] = 8.0
+    q[..., 1] = 8.0
+    k[..., 0] = (256 * (j // 32)).float().view(1, Skv, 1)
+    k[..., 1] = (8 * (j % 32)).float().view(1, Skv, 1)
+    return q.bfloat16(), k.bfloat16(), v, 0.125
+
+
 # ------------------------------------------------- row / elementwise oracles
 
 def rope_oracle(q, k, cos, sin, pos_offset: int = 0, positions=None,
@@ -298,6 +387,22 @@ def rope_oracle(q, k, cos, sin, pos_offset: int = 0, positions=None,
     gq, gk = torch.autograd.grad(
         (q2 * _f32(dq2)).sum() + (k2 * _f32(dk2)).sum(), [qr, kr])
     return q2.detach(), k2.detach(), gq, gk
+
+
+def rope_store_oracle(qkv, cos, sin, positions, Hq: int, Hkv: int,
+                      D: int = 128):
+    """fp32 (q_rot [N,Hq,D], k_rot [N,Hkv,D], v [N,Hkv,D]) of one decode
+    step's fused projection qkv [N, ..., (Hq + 2 Hkv) * D]: q and k rotated
+    at positions[i] (reference.rope_apply), v as is. What decode_rope_store
+    returns (q) and writes to cache rows [slot[i], positions[i]] (k, v)."""
+    n = qkv.shape[0]
+    qq, kk, vv = _f32(qkv).reshape(n, -1).split(
+        [Hq * D, Hkv * D, Hkv * D], dim=-1)
+    pos = torch.as_tensor(positions).detach().cpu().long()
+    q2 = _rope_rows(qq.reshape(n, 1, Hq, D), cos, sin, 0, pos)
+    k2 = _rope_rows(kk.reshape(n, 1, Hkv, D), cos, sin, 0, pos)
+    return (q2.reshape(n, Hq, D), k2.reshape(n, Hkv, D),
+            vv.reshape(n, Hkv, D).clone())
 
 
 def rms_norm_oracle(x, w, dy, eps: float = 1e-5):

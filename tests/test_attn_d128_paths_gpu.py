@@ -260,3 +260,44 @@ def test_fused_qkv_attention_both_metrics(name):
                dv=dv.reshape(B, S, Hkv, D))
     _check(name, got, case)
 
+
+
+# ------------------------------------------------------------- mask probe
+
+def _probe_check(name, o, dv, oracle_o, oracle_dv, hot_o, hot_dv):
+    """testing.mask_probe_inputs: per-row FWD_BOUND / BWD_BOUND against the
+    fp32 oracle on the probe inputs and against the closed form (o row i is
+    the v row of its last visible key, dv row j the group's dout rows whose
+    last visible key is j)."""
+    errs = dict(o=T.row_err(o, oracle_o), o_hot=T.row_err(o, hot_o),
+                dv=T.row_err(dv, oracle_dv), dv_hot=T.row_err(dv, hot_dv))
+    print(f"PARITY {name} probe o row={errs['o']:.5f} "
+          f"row_vs_v={errs['o_hot']:.5f} bound={FWD_BOUND} "
+          f"dv row={errs['dv']:.5f} row_vs_dout={errs['dv_hot']:.5f} "
+          f"bound={BWD_BOUND}")
+    assert o.shape == oracle_o.shape and dv.shape == oracle_dv.shape
+    assert errs["o"] < FWD_BOUND and errs["o_hot"] < FWD_BOUND, errs
+    assert errs["dv"] < BWD_BOUND and errs["dv_hot"] < BWD_BOUND, errs
+
+
+# S = 384: 4-wave forward + dq / dkv kernels; S = 512: fwd4 + dq8 + dkv8f;
+# S = 100: the zero-pad path (4-wave, 28 pad rows)
+@pytest.mark.parametrize("S", [384, 512, 100])
+def test_mask_probe_causal(S):
+    """Scores 8 * j: every row of o is v[row], every row of dv the sum of the
+    group's dout rows at that position. One row's diagonal off by one key
+    gives a per-row error above 1 (tests/test_attn_probe_cpu.py)."""
+    B, Hq, Hkv = 1, 4, 2
+    q, k, v, scale = T.mask_probe_inputs(B, S, S, Hq, Hkv, D, seed=51)
+    gen = torch.Generator(device="cpu").manual_seed(52)
+    dout = torch.randn(B, S, Hq, D, generator=gen).bfloat16()
+    oo, _, _, _, odv = T.attention_oracle(q, k, v, dout, True, scale)
+    dev = torch.device("cuda", 0)
+    qg, kg, vg = (t.to(dev).requires_grad_(True) for t in (q, k, v))
+    o = ops.flash_attention(qg, kg, vg, causal=True, scale=scale)
+    o.backward(dout.to(dev))
+    torch.cuda.synchronize()
+    g = Hq // Hkv
+    hot_o = v.float().repeat_interleave(g, dim=2)
+    hot_dv = dout.float().view(B, S, Hkv, g, D).sum(dim=3)
+    _probe_check(f"causal S{S}", o.detach(), vg.grad, oo, odv, hot_o, hot_dv)

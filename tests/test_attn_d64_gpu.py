@@ -210,3 +210,58 @@ def test_unsupported_head_dim_raises():
     q = torch.zeros(1, 128, 2, 32, device=dev, dtype=torch.bfloat16)
     with pytest.raises(ValueError, match="64"):
         ops.flash_attention(q, q, q, causal=False)
+
+
+# ------------------------------------------------------------- mask probe
+
+def _probe_check(name, o, dv, oracle_o, oracle_dv, hot_o, hot_dv):
+    """testing.mask_probe_inputs: per-row FWD_BOUND / BWD_BOUND against the
+    fp32 oracle on the probe inputs and against the closed form."""
+    from kubeflow_amd.ops import testing as T
+    errs = dict(o=T.row_err(o, oracle_o), o_hot=T.row_err(o, hot_o),
+                dv=T.row_err(dv, oracle_dv), dv_hot=T.row_err(dv, hot_dv))
+    print(f"PARITY {name} probe o row={errs['o']:.5f} "
+          f"row_vs_v={errs['o_hot']:.5f} bound={FWD_BOUND} "
+          f"dv row={errs['dv']:.5f} row_vs_dout={errs['dv_hot']:.5f} "
+          f"bound={BWD_BOUND}")
+    assert o.shape == oracle_o.shape and dv.shape == oracle_dv.shape
+    assert errs["o"] < FWD_BOUND and errs["o_hot"] < FWD_BOUND, errs
+    assert errs["dv"] < BWD_BOUND and errs["dv_hot"] < BWD_BOUND, errs
+
+
+@pytest.mark.parametrize("causal,kv_len", [(True, None), (False, 137)])
+def test_mask_probe(causal, kv_len):
+    """Scores 8 * j (testing.mask_probe_inputs) at S = 200, the pad path.
+    Causal: o row i is v[i] and dv row j the group's dout rows at j.
+    kv_len = 137: every o row is v[136], dv[136] the sum of all dout rows of
+    the group, dv rows past kv_len exact zeros. A mask off by one key in one
+    row gives a per-row error above 1 (tests/test_attn_probe_cpu.py)."""
+    from kubeflow_amd.ops import testing as T
+    B, S, Hq, Hkv = 1, 200, 4, 2
+    g = Hq // Hkv
+    q, k, v, scale = T.mask_probe_inputs(B, S, S, Hq, Hkv, D, seed=61)
+    gen = torch.Generator(device="cpu").manual_seed(62)
+    dout = torch.randn(B, S, Hq, D, generator=gen).bfloat16()
+    oo, _, _, _, odv = T.attention_oracle(q, k, v, dout, causal, scale,
+                                          kv_len=kv_len)
+    dsum = dout.float().view(B, S, Hkv, g, D).sum(dim=3)
+    if causal:
+        hot_o = v.float().repeat_interleave(g, dim=2)
+        hot_dv = dsum
+    else:
+        k[:, kv_len:] = GARBAGE
+        v[:, kv_len:] = GARBAGE
+        hot_o = v.float()[:, kv_len - 1:kv_len].repeat_interleave(
+            g, dim=2).expand(B, S, Hq, D)
+        hot_dv = torch.zeros(B, S, Hkv, D)
+        hot_dv[:, kv_len - 1] = dsum.sum(dim=1)
+    dev = torch.device("cuda", 0)
+    qg, kg, vg = (t.to(dev).requires_grad_(True) for t in (q, k, v))
+    o = ops.flash_attention(qg, kg, vg, causal=causal, scale=scale,
+                            kv_len=kv_len)
+    o.backward(dout.to(dev))
+    torch.cuda.synchronize()
+    _probe_check(f"d64 causal={causal} kv_len={kv_len}", o.detach(), vg.grad,
+                 oo, odv, hot_o, hot_dv)
+    if kv_len is not None:
+        assert not vg.grad[:, kv_len:].any()

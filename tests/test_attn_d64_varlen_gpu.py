@@ -290,3 +290,43 @@ def test_bert_base_engine_batches_mixed_lengths():
             assert torch.allclose(got, want, atol=0.05), (len(p), got, want)
     finally:
         eng.stop()
+
+
+# ------------------------------------------------------------- mask probe
+
+def test_mask_probe_each_sequence_ends_at_its_length():
+    """Scores 8 * j (testing.mask_probe_inputs), lengths (1, 63, 64, 65, 200)
+    at S = 200: every real row of sequence b is v[b, L_b - 1], dv[b, L_b - 1]
+    the sum of the group's real dout rows, and rows past the length exact
+    zeros. Per-row FWD_BOUND / BWD_BOUND against the fp32 oracle per sequence
+    and against the closed form; a length off by one key gives a per-row
+    error above 1 (tests/test_attn_probe_cpu.py)."""
+    lens = (1, 63, 64, 65, 200)
+    B, S, Hq, Hkv = len(lens), 200, 4, 2
+    g = Hq // Hkv
+    q, k, v, scale = T.mask_probe_inputs(B, S, S, Hq, Hkv, D, seed=71)
+    gen = torch.Generator(device="cpu").manual_seed(72)
+    dout = torch.randn(B, S, Hq, D, generator=gen).bfloat16()
+    oo, odv = torch.zeros(B, S, Hq, D), torch.zeros(B, S, Hkv, D)
+    hot_o, hot_dv = torch.zeros(B, S, Hq, D), torch.zeros(B, S, Hkv, D)
+    for b, L in enumerate(lens):
+        r = T.attention_oracle(q[b:b + 1, :L], k[b:b + 1, :L], v[b:b + 1, :L],
+                               dout[b:b + 1, :L], False, scale)
+        oo[b, :L], odv[b, :L] = r[0][0], r[4][0]
+        hot_o[b, :L] = v[b, L - 1].float().repeat_interleave(g, dim=0)
+        hot_dv[b, L - 1] = dout[b, :L].float().view(L, Hkv, g, D).sum(
+            dim=(0, 2))
+        k[b, L:] = GARBAGE
+        v[b, L:] = GARBAGE
+    sl = torch.tensor(lens, dtype=torch.int32, device=_dev())
+    o, _, _, dv = _gpu_run(q, k, v, dout, scale=scale, seq_lens=sl)
+    errs = dict(o=T.row_err(o, oo), o_hot=T.row_err(o, hot_o),
+                dv=T.row_err(dv, odv), dv_hot=T.row_err(dv, hot_dv))
+    print(f"PARITY varlen probe o row={errs['o']:.5f} "
+          f"row_vs_v={errs['o_hot']:.5f} bound={FWD_BOUND} "
+          f"dv row={errs['dv']:.5f} row_vs_dout={errs['dv_hot']:.5f} "
+          f"bound={BWD_BOUND}")
+    assert errs["o"] < FWD_BOUND and errs["o_hot"] < FWD_BOUND, errs
+    assert errs["dv"] < BWD_BOUND and errs["dv_hot"] < BWD_BOUND, errs
+    for b, L in enumerate(lens):
+        assert not o[b, L:].any() and not dv[b, L:].any(), (b, L)
