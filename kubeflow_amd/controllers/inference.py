@@ -171,11 +171,13 @@ class InferenceServiceReconciler(Reconciler):
             "world_size": 1,
         }
         if pred.get("quantization"):
-            # W8A16 fp8 decode weights (ops/csrc/skinny_gemm.hip q8 path)
-            if pred["quantization"] != "fp8":
+            # W8A16 fp8 or W4A16 MXFP4 decode weights
+            # (ops/csrc/skinny_gemm.hip q8 and q4 paths)
+            if pred["quantization"] not in ("fp8", "mxfp4"):
                 set_condition(svc, "Failed", "True", "InvalidQuantization",
                               f"unsupported quantization "
-                              f"{pred['quantization']!r} (supported: fp8)")
+                              f"{pred['quantization']!r} "
+                              "(supported: fp8, mxfp4)")
                 self.scheduler.release(uid)
                 self.store.update(svc, check_version=False)
                 return

@@ -215,7 +215,8 @@ class MoEMLP(nn.Module):
             out = out + gatew[:, self.e_lo + el].unsqueeze(1) * y
         return out.view(N, S, h)
 
-    def routed_decode_ok(self, x, q8: bool = False) -> bool:
+    def routed_decode_ok(self, x, q8: bool = False,
+                         q4: bool = False) -> bool:
         """True if decode_routed(x) takes ops.moe_experts_decode: EP = 1, the
         moe.hip path usable for x's rows (bf16 on the GPU), at most 32 rows
         and both banks within the grouped skinny kernels' shapes."""
@@ -227,24 +228,26 @@ class MoEMLP(nn.Module):
                                       cfg.top_k)
                 and self.experts_w13.dtype == x.dtype
                 and self.gate.weight.dtype == x.dtype
-                and ops.grouped_skinny_ok(T, 2 * f, h, x.dtype, q8=q8)
-                and ops.grouped_skinny_ok(T, h, f, x.dtype, q8=q8))
+                and ops.grouped_skinny_ok(T, 2 * f, h, x.dtype, q8=q8, q4=q4)
+                and ops.grouped_skinny_ok(T, h, f, x.dtype, q8=q8, q4=q4))
 
-    def decode_routed(self, x, q8=None):
+    def decode_routed(self, x, q8=None, q4=None):
         """Capture-safe routed decode: only the k experts a token selects run
         on it, and an expert no token selects streams none of its weights.
         ops.moe_experts_decode keeps the expert offsets on the device, so a
         captured graph follows each replay's routing. q8: the two banks
-        quantized per row (see ops.moe_experts_decode). Where
+        quantized per row, q4: in MXFP4 (see ops.moe_experts_decode). Where
         routed_decode_ok does not hold (the CPU, EP, more than 32 rows, bank
         shapes the kernels reject) this is decode_dense on the bf16 banks."""
-        if not self.routed_decode_ok(x, q8=q8 is not None):
+        if not self.routed_decode_ok(x, q8=q8 is not None,
+                                     q4=q4 is not None):
             return self.decode_dense(x)
         N, S, h = x.shape
         xf = x.reshape(N * S, h)
         logits = torch.nn.functional.linear(xf, self.gate.weight)
         out = ops.moe_experts_decode(xf, logits, self.experts_w13,
-                                     self.experts_w2, self.cfg.top_k, q8=q8)
+                                     self.experts_w2, self.cfg.top_k, q8=q8,
+                                     q4=q4)
         return out.view(N, S, h)
 
 

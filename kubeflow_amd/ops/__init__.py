@@ -30,7 +30,8 @@ __all__ = [
     "rms_norm", "layer_norm", "rope", "flash_attention", "attention_decode",
     "flash_attention_rect", "skinny_linear", "kv_store",
     "decode_rope_store", "skinny_linear_q8", "quantize_fp8_rows",
-    "dequantize_fp8_rows",
+    "dequantize_fp8_rows", "skinny_linear_q4", "quantize_mxfp4_rows",
+    "dequantize_mxfp4_rows",
     "cross_entropy", "fused_adamw", "rope_cos_sin", "native_available",
     "masked_attention",
     "swiglu", "fused_qkv_attention",
@@ -38,6 +39,7 @@ __all__ = [
     "MoeRouting", "moe_route", "moe_gather", "moe_combine", "grouped_linear",
     "moe_experts", "moe_native_ok",
     "grouped_skinny_ok", "grouped_skinny_linear", "grouped_skinny_linear_q8",
+    "grouped_skinny_linear_q4",
     "moe_experts_decode",
 ]
 
@@ -310,19 +312,40 @@ def kv_store(cache_k: torch.Tensor, cache_v: torch.Tensor,
     cache_v[slots.long(), positions] = v.reshape(n, *cache_v.shape[2:])
 
 
-def _skinny_shape_ok(rows: int, N: int, K: int, q8: bool) -> bool:
+def _skinny_shape_ok(rows: int, N: int, K: int, family) -> bool:
     """The shape rule of skinny_gemm.hip for `rows` batch rows against
-    [N, K] weights: the LDS kernel takes K % 512 == 0 (q8: K % 1024 == 0)
-    up to 32 rows, the direct bf16 kernel K % 32 == 0 up to 16 rows."""
+    [N, K] weights, per kernel family: False or None is bf16 (the LDS kernel
+    takes K % 512 == 0 up to 32 rows, the direct kernel K % 32 == 0 up to 16
+    rows), True or "q8" the fp8 family, "q4" the MXFP4 one (each its own
+    rule, today both K % 1024 == 0 up to 32 rows)."""
     if not 1 <= rows <= 32 or N % 16:
         return False
-    if q8:
+    if family == "q4":
+        return K % 1024 == 0
+    if family:
         return K % 1024 == 0
     return K % 512 == 0 or (K % 32 == 0 and rows <= 16)
 
 
+def _skinny_family(scale):
+    """Kernel family of a weight by its scale tensor: None bf16, a uint8
+    scale MXFP4 ("q4"), a float one fp8 ("q8")."""
+    if scale is None:
+        return None
+    return "q4" if scale.dtype == torch.uint8 else "q8"
+
+
+def _dequantize_rows(w, scale, dtype):
+    """The bf16 rows of a quantized weight: a uint8 scale is MXFP4 (e8m0 per
+    32 along K), a float one fp8 (per row)."""
+    if scale.dtype == torch.uint8:
+        return dequantize_mxfp4_rows(w, scale, dtype)
+    return dequantize_fp8_rows(w, scale, dtype)
+
+
 def _skinny(x, w, scale, residual):
-    """Shared body of the two skinny linears; scale None = bf16 weight."""
+    """Shared body of the skinny linears; scale None = bf16 weight, fp32 =
+    fp8 rows, uint8 = MXFP4 rows (w then holds two elements per byte)."""
     shape = x.shape
     M = 1
     for d in shape[:-1]:
@@ -330,8 +353,8 @@ def _skinny(x, w, scale, residual):
     K = shape[-1]
     N = w.shape[0]
     if (not _use_native(x) or x.dtype != torch.bfloat16
-            or not _skinny_shape_ok(M, N, K, scale is not None)):
-        wb = w if scale is None else dequantize_fp8_rows(w, scale, x.dtype)
+            or not _skinny_shape_ok(M, N, K, _skinny_family(scale))):
+        wb = w if scale is None else _dequantize_rows(w, scale, x.dtype)
         y = torch.nn.functional.linear(x, wb)
         return y + residual if residual is not None else y
     lib = _backend.require()
@@ -349,6 +372,11 @@ def _skinny(x, w, scale, residual):
             lib.kf_skinny_gemm(_p(y), _p(x2), _p(w), _p(r2), M, N, K,
                                K, 0, 0, _stream()),
             "skinny_gemm")
+    elif scale.dtype == torch.uint8:
+        _backend.check(
+            lib.kf_skinny_gemm_q4(_p(y), _p(x2), _p(w), _p(scale), _p(r2),
+                                  M, N, K, K, 0, 0, _stream()),
+            "skinny_gemm_q4")
     else:
         _backend.check(
             lib.kf_skinny_gemm_q8(_p(y), _p(x2), _p(w), _fp(scale), _p(r2),
@@ -396,6 +424,87 @@ def skinny_linear_q8(x: torch.Tensor, w8: torch.Tensor,
     (skinny_gemm.hip kf_skinny_q8_kernel); activations stay bf16 and the
     MFMA runs bf16 (W8A16). Serving-only, behind KF_SERVE_QUANT=fp8."""
     return _skinny(x, w8, scale, residual)
+
+
+def quantize_mxfp4_rows(w: torch.Tensor):
+    """OCP MXFP4 weight quantization for the W4A16 decode path: e2m1
+    elements, one e8m0 scale per 32 along K. w [N, K], K % 32 == 0 ->
+    (w4 uint8 [N, K/2], scale uint8 [N, K/32]). Element 2i of a row is the
+    low nibble of byte i, 2i+1 the high one; scale byte b means 2^(b-127).
+
+    Per block, b = clamp(floor(log2(absmax)) - 2 + 127, 1, 254) (127 for an
+    all-zero block) and the elements are w / 2^(b-127) rounded to
+    nearest-even on +-{0, .5, 1, 1.5, 2, 3, 4, 6}, saturating at +-6. Pure
+    torch, on w's device."""
+    if w.dim() != 2 or w.shape[1] % 32:
+        raise ValueError("quantize_mxfp4_rows: w must be [N, K] with "
+                         f"K % 32 == 0, got {tuple(w.shape)}")
+    with torch.no_grad():  # as quantize_fp8_rows: no retained fp32 temps
+        N, K = w.shape
+        blk = w.detach().float().reshape(N, K // 32, 32)
+        amax = blk.abs().amax(dim=2)
+        # amax = m * 2^e with m in [0.5, 1): floor(log2(amax)) = e - 1
+        e = torch.frexp(amax)[1]
+        b = torch.where(amax > 0, (e - 3 + 127).clamp(1, 254),
+                        torch.full_like(e, 127))
+        v = blk / torch.ldexp(torch.ones_like(amax), b - 127).unsqueeze(2)
+        a = v.abs()
+        # the grid step is .5 below 2, 1 below 4, 2 above; torch.round is
+        # half-to-even, and on every tie the even multiple is the e2m1 value
+        # with mantissa bit 0
+        step = torch.where(a < 2, 0.5, torch.where(a < 4, 1.0, 2.0))
+        q = ((a / step).round() * step).clamp(max=6.0)
+        code = torch.where(q < 2, q * 2, torch.where(q < 4, q + 2, q / 2 + 4))
+        code = code.to(torch.uint8).reshape(N, K)
+        # the sign bit only on a nonzero code: -0 is never produced
+        code = code | (((v.reshape(N, K) < 0) & (code > 0)).to(torch.uint8)
+                       << 3)
+        w4 = code[:, 0::2] | (code[:, 1::2] << 4)
+        return w4.contiguous(), b.to(torch.uint8).contiguous()
+
+
+def dequantize_mxfp4_rows(w4: torch.Tensor, scale: torch.Tensor,
+                          dtype=torch.bfloat16) -> torch.Tensor:
+    """[N, K] values of quantize_mxfp4_rows' pair; exact in bf16 and fp32 (an
+    e2m1 value has two significant bits, the scale is a power of two)."""
+    N, K = w4.shape[0], w4.shape[1] * 2
+    code = torch.stack((w4 & 15, w4 >> 4), dim=2).reshape(N, K)
+    # arithmetic, not a table on the host: the fallback of the q4 linears
+    # runs this inside captured graphs. exponent field 0 is the subnormal
+    # pair {0, .5}, else (1 + man / 2) * 2^(exp - 1)
+    exp, man = ((code >> 1) & 3).float(), (code & 1).float()
+    mag = torch.where(exp == 0, man * 0.5,
+                      (1 + man * 0.5) * torch.exp2(exp - 1))
+    v = mag * (1 - 2 * (code >> 3).float())
+    s = torch.exp2(scale.float() - 127)
+    v = v.reshape(N, K // 32, 32) * s.unsqueeze(2)
+    return v.reshape(N, K).to(dtype)
+
+
+def _check_mxfp4(op: str, x, w4, scale) -> None:
+    if (w4.dim() != 2 or w4.dtype != torch.uint8 or scale.dtype != torch.uint8
+            or (w4.shape[1] * 2) % 32
+            or scale.shape != (w4.shape[0], w4.shape[1] // 16)
+            or x.shape[-1] != w4.shape[1] * 2
+            or not w4.is_contiguous() or not scale.is_contiguous()):
+        raise ValueError(
+            f"{op}: x {tuple(x.shape)}, w4 {tuple(w4.shape)} {w4.dtype} and "
+            f"scale {tuple(scale.shape)} {scale.dtype} do not agree (w4 "
+            "uint8 [N, K/2], scale uint8 [N, K/32], both contiguous)")
+
+
+def skinny_linear_q4(x: torch.Tensor, w4: torch.Tensor, scale: torch.Tensor,
+                     residual: Optional[torch.Tensor] = None
+                     ) -> torch.Tensor:
+    """MXFP4 decode linear y = x @ dequant(w4, scale)^T (+ residual), the
+    pair quantize_mxfp4_rows returns: a quarter of the bf16 weight bytes
+    (skinny_gemm.hip kf_skinny_q4_kernel). The weights convert to bf16 in
+    registers, exactly, and the MFMA runs bf16 (W4A16), so y is
+    skinny_linear's on the dequantized weights up to summation order.
+    Serving-only, behind KF_SERVE_QUANT=mxfp4. Off the GPU and for shapes the
+    kernel rejects: F.linear on the dequantized weights."""
+    _check_mxfp4("skinny_linear_q4", x, w4, scale)
+    return _skinny(x, w4, scale, residual)
 
 
 def decode_rope_store(qkv: torch.Tensor, cache_k: torch.Tensor,
@@ -1598,19 +1707,23 @@ GROUPED_SKINNY_MAX_ROWS = 32
 
 
 def grouped_skinny_ok(T: int, N: int, K: int, dtype,
-                      q8: bool = False) -> bool:
-    """True if kf_skinny_gemm_grouped (q8: kf_skinny_gemm_grouped_q8) takes
-    T token rows against [., N, K] banks: what a caller asks before it
-    captures a graph, since the fallback of grouped_skinny_linear syncs. The
-    LDS kernel needs K % 512 == 0 (q8: K % 1024 == 0) and T <= 32, the direct
-    bf16 kernel K % 32 == 0 and T <= 16."""
+                      q8: bool = False, q4: bool = False) -> bool:
+    """True if kf_skinny_gemm_grouped (q8: kf_skinny_gemm_grouped_q8, q4:
+    kf_skinny_gemm_grouped_q4) takes T token rows against [., N, K] banks:
+    what a caller asks before it captures a graph, since the fallback of
+    grouped_skinny_linear syncs. The LDS kernel needs K % 512 == 0 (q8 and
+    q4: K % 1024 == 0) and T <= 32, the direct bf16 kernel K % 32 == 0 and
+    T <= 16."""
     return (dtype == torch.bfloat16 and N >= 16 and K >= 32
-            and _skinny_shape_ok(T, N, K, q8))
+            and _skinny_shape_ok(T, N, K, "q4" if q4 else q8))
 
 
 def _grouped_skinny(x, w, scale, offsets, max_rows, rows, out, n, N, K):
-    """Shared body of the two grouped linears; scale None = bf16 bank."""
-    name = "grouped_skinny_linear" + ("" if scale is None else "_q8")
+    """Shared body of the grouped linears; scale None = bf16 bank, fp32 =
+    fp8 rows, uint8 = MXFP4 rows."""
+    q4 = scale is not None and scale.dtype == torch.uint8
+    name = "grouped_skinny_linear" + (
+        "" if scale is None else "_q4" if q4 else "_q8")
     if (x.dim() != 2 or x.shape[1] != K or offsets.dim() != 1
             or offsets.numel() != n + 1
             or (rows is not None and rows.dim() != 1)):
@@ -1628,9 +1741,9 @@ def _grouped_skinny(x, w, scale, offsets, max_rows, rows, out, n, N, K):
     native = (_use_native(x) and offsets.dtype == torch.int32
               and (rows is None or rows.dtype == torch.int32)
               and grouped_skinny_ok(max_rows, N, K, x.dtype,
-                                    q8=scale is not None))
+                                    q8=scale is not None and not q4, q4=q4))
     if not native:
-        wb = w if scale is None else dequantize_fp8_rows(w, scale, x.dtype)
+        wb = w if scale is None else _dequantize_rows(w, scale, x.dtype)
         y = reference.grouped_linear_offsets(x, wb.reshape(n, N, K), offsets,
                                              rows)
         if out is None:
@@ -1650,6 +1763,13 @@ def _grouped_skinny(x, w, scale, offsets, max_rows, rows, out, n, N, K):
                 _p(out), _p(x), _p(w), _i32p(offsets), _i32p(rows), n,
                 max_rows, total, x.shape[0], N, K, _stream()),
             "skinny_gemm_grouped")
+    elif q4:
+        _backend.check(
+            lib.kf_skinny_gemm_grouped_q4(
+                _p(out), _p(x), _p(w), _p(scale), _i32p(offsets),
+                _i32p(rows), n, max_rows, total, x.shape[0], N, K,
+                _stream()),
+            "skinny_gemm_grouped_q4")
     else:
         _backend.check(
             lib.kf_skinny_gemm_grouped_q8(
@@ -1716,10 +1836,33 @@ def grouped_skinny_linear_q8(x: torch.Tensor, w8: torch.Tensor,
                            w8.shape[0] // n, w8.shape[1])
 
 
+def grouped_skinny_linear_q4(x: torch.Tensor, w4: torch.Tensor,
+                             scale: torch.Tensor, offsets: torch.Tensor,
+                             max_rows: int,
+                             rows: Optional[torch.Tensor] = None, *,
+                             out: Optional[torch.Tensor] = None
+                             ) -> torch.Tensor:
+    """grouped_skinny_linear on an MXFP4 bank: w4 uint8 [n * N, K/2] and
+    scale uint8 [n * N, K/32], quantize_mxfp4_rows of the bank flattened to
+    rows (expert e, column j is row e * N + j); n = offsets.numel() - 1. Each
+    expert's rows are skinny_linear_q4's on the bank slice, bit for bit."""
+    n = offsets.numel() - 1
+    if (w4.dim() != 2 or n < 1 or w4.shape[0] % n or w4.dtype != torch.uint8
+            or scale.dtype != torch.uint8 or (w4.shape[1] * 2) % 32
+            or scale.shape != (w4.shape[0], w4.shape[1] // 16)
+            or not w4.is_contiguous() or not scale.is_contiguous()):
+        raise ValueError(
+            f"grouped_skinny_linear_q4: w4 {tuple(w4.shape)} {w4.dtype}, "
+            f"scale {tuple(scale.shape)} {scale.dtype} and {n} experts do "
+            "not agree")
+    return _grouped_skinny(x, w4, scale, offsets, max_rows, rows, out, n,
+                           w4.shape[0] // n, w4.shape[1] * 2)
+
+
 @torch.no_grad()
 def moe_experts_decode(x: torch.Tensor, logits: torch.Tensor,
                        w13: torch.Tensor, w2: torch.Tensor, top_k: int,
-                       q8=None) -> torch.Tensor:
+                       q8=None, q4=None) -> torch.Tensor:
     """moe_experts for the decode step, without a host sync: x [T, h],
     logits [T, E], full banks w13 [E, 2f, h] and w2 [E, h, f] -> [T, h].
 
@@ -1728,12 +1871,21 @@ def moe_experts_decode(x: torch.Tensor, logits: torch.Tensor,
     the grouped w2 GEMM; moe_combine. Every buffer is sized from T, k and the
     weight shapes, so a graph captured on one routing replays any other.
     q8 = ((w13_8, w13_scale), (w2_8, w2_scale)), the banks through
-    quantize_fp8_rows on their [E * out, in] views, selects the fp8 kernels.
+    quantize_fp8_rows on their [E * out, in] views, selects the fp8 kernels;
+    q4, the same pairs from quantize_mxfp4_rows, the MXFP4 ones.
     Inference only. For capture the caller checks grouped_skinny_ok for both
     banks first."""
+    if q8 is not None and q4 is not None:
+        raise ValueError("moe_experts_decode: q8 and q4 exclude each other")
     T = x.shape[0]
     routing = moe_route(logits, top_k, 0, w13.shape[0], sync=False)
-    if q8 is None:
+    if q4 is not None:
+        (w13_4, s13), (w2_4, s2) = q4
+        h13 = grouped_skinny_linear_q4(x, w13_4, s13, routing.offsets, T,
+                                       routing.src)
+        y = grouped_skinny_linear_q4(swiglu(h13), w2_4, s2, routing.offsets,
+                                     T)
+    elif q8 is None:
         h13 = grouped_skinny_linear(x, w13, routing.offsets, T, routing.src)
         y = grouped_skinny_linear(swiglu(h13), w2, routing.offsets, T)
     else:

@@ -10,11 +10,13 @@
 // operand rows = the M batch rows, zero-padded to the 16- or 32-row tile),
 // then a reduction over the waves through LDS.
 //
-// Three kernel families, each with a plain and a grouped __global__ kernel:
+// Four kernel families, each with a plain and a grouped __global__ kernel:
 //   direct   K % 32 == 0, M <= 16        kf_sk_direct_body<SKW>
 //   LDS bf16 K % 512 == 0, M <= 32       two kernels, kept in step by hand
-//   LDS q8   K % 1024 == 0, M <= 32      kf_sk_q8_body<MT>
-// The direct and q8 families have one __device__ body that both kernels run.
+//   LDS q8   K % 1024 == 0, M <= 32      kf_sk_q8_body<MT>    (e4m3 weights)
+//   LDS q4   K % 1024 == 0, M <= 32      kf_sk_q4_body<MT>    (MXFP4 weights)
+// The direct, q8 and q4 families have one __device__ body that both kernels
+// run.
 // The LDS bf16 family does not: inlined from a shared body its 32-row
 // instantiations compile to another prefetch sequence, which measured 3.6%
 // slower on one grouped shape (profiles/skinny_shared_body.md).
@@ -385,6 +387,166 @@ __device__ __forceinline__ void kf_sk_q8_body(
 }
 
 // ---------------------------------------------------------------------
+// W4A16 MXFP4 body: W stored as OCP e2m1 nibbles (element 2i in the low
+// nibble of byte i, 2i+1 in the high one) with one e8m0 scale byte per 32
+// elements along K (wscale [N, K/32] row-major, byte b = 2^(b-127)). e2m1 has
+// two significant bits and the scale only moves the exponent, so
+// dequant(w4, scale) is exact in bf16: this computes the product the bf16
+// kernel gives on the dequantized weights, with the same two roundings (fp32
+// accumulate, one bf16 store) and no scale multiply in the epilogue.
+//
+// The skeleton is the q8 body's (8 waves, one 16-column tile, in-block K
+// split, double-buffered LDS tile, one barrier per 1024-k chunk, the slice
+// layout ke0 = wv*128 + hi4*8 + 32*si). What differs:
+//   * a 1024-k chunk is 512 B per row, 8 KB per block: ONE b128 load per
+//     lane, half-waves covering rows {2wv, 2wv+1} (16 B = 32 elements = one
+//     MX block). Half the bytes of a q8 chunk would be in flight, so the
+//     register staging runs TWO chunks ahead: chunk ch+2 is loaded while
+//     chunk ch is multiplied and chunk ch+1 waits in registers for its LDS
+//     buffer. The chunk loop is unrolled by two so the two staging registers
+//     swap roles by name, not by a move that would wait for the newest load.
+//     W's load is issued after the A loads of the step, so the wait for those
+//     (vmcnt counts in order) leaves it outstanding.
+//   * a lane's fragment (8 consecutive k) is one 32-bit LDS word; the padded
+//     row stride (132 words) puts lane (l15, hi4) on bank 4*l15 + hi4: the 64
+//     lanes of a wave read 64 different banks.
+//   * the four fragments of a chunk lie in MX blocks wv*4 .. wv*4+3 of row
+//     l15: one aligned 32-bit word of scale bytes per lane per chunk, loaded
+//     straight from global one chunk ahead, with the A fragments.
+//   * a fragment is four v_cvt_scalef32_pk_bf16_fp4 (byte_sel 0..3 of the
+//     word), the scale operand the fp32 with bit pattern b << 23.
+
+#define SK4_KC 1024                 // fp4 K elems per staged chunk
+#define SK4_ROWB (SK4_KC / 2)       // ... = 512 B per row
+#define SK4_STRIDE (SK4_ROWB + 16)  // row slice bytes + pad (132 words)
+
+typedef __bf16 kf_bf16x2s __attribute__((ext_vector_type(2)));
+
+// 8 e2m1 values of one word (element j in nibble j) times 2^(sbyte - 127)
+__device__ __forceinline__ kf_bf16x8s kf_fp4x8_to_bf16x8(unsigned int w,
+                                                         unsigned int sbyte) {
+  const float sc = __builtin_bit_cast(float, sbyte << 23);
+  union {
+    kf_bf16x2s p[4];
+    kf_bf16x8s v;
+  } out;
+  out.p[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 0);
+  out.p[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 1);
+  out.p[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 2);
+  out.p[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 3);
+  return out.v;
+}
+
+// p.ldw counts fp4 elements: W rows are ldw / 2 bytes, scale rows ldw / 32
+template <int MT>
+__device__ __forceinline__ void kf_sk_q4_body(
+    const kf_sk_prob& p, const unsigned char* __restrict__ w4,
+    const unsigned char* __restrict__ wscale,
+    unsigned char (&wbuf4)[2][SK_NT][SK4_STRIDE],
+    float (&red)[SKL_W][MT][SK_NT]) {
+  const int64_t n0 = (int64_t)blockIdx.x * SK_NT;
+  const int tid = threadIdx.x;
+  const int wv = tid / KF_WAVE;
+  const int lane = tid & (KF_WAVE - 1);
+  const int l15 = lane & 15;
+  const int hi4 = lane >> 4;
+
+  const int NMT = MT / 16;
+  kf_f32x4s acc[NMT];
+  bool arow_ok[NMT];
+  const unsigned short* arow[NMT];
+#pragma unroll
+  for (int t = 0; t < NMT; ++t) {
+    acc[t] = kf_f32x4s{0.f, 0.f, 0.f, 0.f};
+    arow_ok[t] = l15 + 16 * t < p.M;
+    arow[t] = p.a + kf_sk_a_row(p.a_rows,
+                                p.lo + (arow_ok[t] ? l15 + 16 * t : 0),
+                                p.a_nrows) * p.lda;
+  }
+  const kf_bf16x8s zero8 = kf_bf16x8s{0, 0, 0, 0, 0, 0, 0, 0};
+  // writer: half-wave h of wave wv stages row 2wv + h, 16 B per lane
+  const int wrow = 2 * wv + (lane >> 5);
+  const int wcol = (lane & 31) * 16;
+  const unsigned char* wr = w4 + (n0 + wrow) * (p.ldw >> 1) + wcol;
+  // this lane's scale word: MX blocks wv*4 .. wv*4+3 of row l15, per chunk
+  const unsigned char* sr = wscale + (n0 + l15) * (p.ldw >> 5) + wv * 4;
+
+  const int64_t nch = p.K / SK4_KC;
+  const int ke0 = wv * 128 + hi4 * 8;  // k slices at +0,+32,+64,+96
+  kf_bf16x8s af[4][NMT];
+#pragma unroll
+  for (int si = 0; si < 4; ++si)
+#pragma unroll
+    for (int t = 0; t < NMT; ++t)
+      af[si][t] = arow_ok[t]
+          ? *reinterpret_cast<const kf_bf16x8s*>(arow[t] + ke0 + 32 * si)
+          : zero8;
+  unsigned int sf = *reinterpret_cast<const unsigned int*>(sr);
+  const kf_u32x4q zero4 = kf_u32x4q{0u, 0u, 0u, 0u};
+  kf_u32x4q sa = *reinterpret_cast<const kf_u32x4q*>(wr);
+  kf_u32x4q sb = zero4;
+  *reinterpret_cast<kf_u32x4q*>(&wbuf4[0][wrow][wcol]) = sa;
+  if (nch > 1) sa = *reinterpret_cast<const kf_u32x4q*>(wr + SK4_ROWB);
+
+  // one chunk: `cur` holds chunk ch+1 (loaded a step ago), `nxt` takes ch+2
+  auto step = [&](int64_t ch, kf_u32x4q& cur, kf_u32x4q& nxt)
+                  __attribute__((always_inline)) {
+    kf_bf16x8s acur[4][NMT];
+#pragma unroll
+    for (int si = 0; si < 4; ++si)
+#pragma unroll
+      for (int t = 0; t < NMT; ++t) acur[si][t] = af[si][t];
+    const unsigned int scur = sf;
+    if (ch + 1 < nch) {
+#pragma unroll
+      for (int si = 0; si < 4; ++si)
+#pragma unroll
+        for (int t = 0; t < NMT; ++t)
+          if (arow_ok[t])
+            af[si][t] = *reinterpret_cast<const kf_bf16x8s*>(
+                arow[t] + (ch + 1) * SK4_KC + ke0 + 32 * si);
+      sf = *reinterpret_cast<const unsigned int*>(sr + (ch + 1) * 32);
+    }
+    if (ch + 2 < nch)
+      nxt = *reinterpret_cast<const kf_u32x4q*>(wr + (ch + 2) * SK4_ROWB);
+    __syncthreads();  // one per chunk, as in the bf16 and q8 kernels
+#pragma unroll
+    for (int si = 0; si < 4; ++si) {
+      const unsigned int word = *reinterpret_cast<const unsigned int*>(
+          &wbuf4[ch & 1][l15][(ke0 + 32 * si) >> 1]);
+      kf_bf16x8s wf = kf_fp4x8_to_bf16x8(word, (scur >> (8 * si)) & 0xffu);
+#pragma unroll
+      for (int t = 0; t < NMT; ++t)
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(acur[si][t], wf,
+                                                         acc[t], 0, 0, 0);
+    }
+    if (ch + 1 < nch)
+      *reinterpret_cast<kf_u32x4q*>(&wbuf4[(ch + 1) & 1][wrow][wcol]) = cur;
+  };
+  for (int64_t ch = 0; ch < nch; ch += 2) {
+    step(ch, sa, sb);
+    if (ch + 1 < nch) step(ch + 1, sb, sa);
+  }
+#pragma unroll
+  for (int t = 0; t < NMT; ++t)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      red[wv][16 * t + hi4 * 4 + j][l15] = acc[t][j];
+  __syncthreads();
+  if (tid < MT * SK_NT) {
+    const int row = tid / SK_NT, col = tid % SK_NT;
+    if (row < p.M && n0 + col < p.N) {
+      float s = 0.f;
+#pragma unroll
+      for (int ww = 0; ww < SKL_W; ++ww) s += red[ww][row][col];
+      const int64_t at = (int64_t)(p.lo + row) * p.ldc + n0 + col;
+      if (p.res) s += kf_bf16_to_f32(p.res[at]);
+      p.c[at] = kf_f32_to_bf16(s);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------
 // Plain kernels: one problem, every block the same M rows.
 
 template <int SKW>
@@ -430,6 +592,45 @@ KF_EXPORT int kf_skinny_gemm_q8(void* c, const void* a, const void* w8,
                      lda, ldw, ldc)
   if (M > 16) KF_SKQ_LAUNCH(32);
   else KF_SKQ_LAUNCH(16);
+  return (int)hipGetLastError();
+}
+
+template <int MT>
+__global__ __launch_bounds__(SKL_W * 64, 2) void kf_skinny_q4_kernel(
+    unsigned short* __restrict__ c, const unsigned short* __restrict__ a,
+    const unsigned char* __restrict__ w4,
+    const unsigned char* __restrict__ wscale,
+    const unsigned short* __restrict__ res,
+    int M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldc) {
+  __shared__ __attribute__((aligned(16)))
+      unsigned char wbuf4[2][SK_NT][SK4_STRIDE];
+  __shared__ float red[SKL_W][MT][SK_NT];
+  kf_sk_q4_body<MT>(
+      kf_sk_prob{c, a, res, nullptr, 0, 0, M, N, K, lda, ldw, ldc}, w4,
+      wscale, wbuf4, red);
+}
+
+// w4 [N, ldw / 2] bytes, wscale [N, ldw / 32] e8m0 bytes; ldw in fp4 elements
+KF_EXPORT int kf_skinny_gemm_q4(void* c, const void* a, const void* w4,
+                                const unsigned char* wscale, const void* res,
+                                int64_t M, int64_t N, int64_t K, int64_t lda,
+                                int64_t ldw, int64_t ldc, void* stream) {
+  if (M < 1 || M > 32 || K < SK4_KC || K % SK4_KC || N < SK_NT || N % SK_NT)
+    return (int)hipErrorInvalidValue;
+  if (lda == 0) lda = K;
+  if (ldw == 0) ldw = K;
+  if (ldc == 0) ldc = N;
+  // 16 B W loads and 4 B scale loads: rows of ldw / 2 and ldw / 32 bytes
+  if (ldw < K || ldw % 128 || lda % 8) return (int)hipErrorInvalidValue;
+  dim3 grid((unsigned)(N / SK_NT), 1, 1);
+#define KF_SK4_LAUNCH(MT)                                                \
+  hipLaunchKernelGGL(kf_skinny_q4_kernel<MT>, grid, dim3(SKL_W * 64), 0, \
+                     (hipStream_t)stream, (unsigned short*)c,            \
+                     (const unsigned short*)a, (const unsigned char*)w4, \
+                     wscale, (const unsigned short*)res, (int)M, N, K,   \
+                     lda, ldw, ldc)
+  if (M > 16) KF_SK4_LAUNCH(32);
+  else KF_SK4_LAUNCH(16);
   return (int)hipGetLastError();
 }
 
@@ -651,7 +852,28 @@ __global__ __launch_bounds__(SKL_W * 64, 2) void kf_skinny_q8_grouped_kernel(
                     wscale_bank + (int64_t)blockIdx.y * N, wbuf8, red);
 }
 
-// shape limits shared by the two grouped entry points; the row counts are
+// w4 is the bank flattened to [n_groups * N, K / 2] bytes with its e8m0 scales
+// [n_groups * N, K / 32]: expert e, column n is row e * N + n of both
+template <int MT>
+__global__ __launch_bounds__(SKL_W * 64, 2) void kf_skinny_q4_grouped_kernel(
+    unsigned short* __restrict__ c, const unsigned short* __restrict__ a,
+    const unsigned char* __restrict__ w4_bank,
+    const unsigned char* __restrict__ wscale_bank,
+    const int* __restrict__ offsets, const int* __restrict__ a_rows,
+    int max_rows, int total_rows, int a_nrows, int64_t N, int64_t K) {
+  __shared__ __attribute__((aligned(16)))
+      unsigned char wbuf4[2][SK_NT][SK4_STRIDE];
+  __shared__ float red[SKL_W][MT][SK_NT];
+  const kf_sk_group g =
+      kf_sk_group_range(offsets, blockIdx.y, max_rows, total_rows);
+  if (g.m == 0) return;  // before any load of W (see the direct kernel)
+  kf_sk_q4_body<MT>(kf_sk_group_prob(c, a, a_rows, a_nrows, g, N, K),
+                    w4_bank + (int64_t)blockIdx.y * N * (K >> 1),
+                    wscale_bank + (int64_t)blockIdx.y * N * (K >> 5), wbuf4,
+                    red);
+}
+
+// shape limits shared by the grouped entry points; the row counts are
 // int32 in the kernels
 static bool kf_sk_grouped_ok(int64_t n_groups, int64_t max_rows,
                              int64_t total_rows, int64_t a_nrows, int64_t N) {
@@ -713,5 +935,30 @@ KF_EXPORT int kf_skinny_gemm_grouped_q8(void* c, const void* a,
                      (int)max_rows, (int)total_rows, (int)a_nrows, N, K)
   if (max_rows > 16) KF_SKGQ_LAUNCH(32);
   else KF_SKGQ_LAUNCH(16);
+  return (int)hipGetLastError();
+}
+
+// as above with w4 [n_groups * N, K / 2] e2m1 pairs and wscale e8m0
+// [n_groups * N, K / 32]
+KF_EXPORT int kf_skinny_gemm_grouped_q4(void* c, const void* a,
+                                        const void* w4,
+                                        const unsigned char* wscale,
+                                        const int* offsets, const int* a_rows,
+                                        int64_t n_groups, int64_t max_rows,
+                                        int64_t total_rows, int64_t a_nrows,
+                                        int64_t N, int64_t K, void* stream) {
+  if (!kf_sk_grouped_ok(n_groups, max_rows, total_rows, a_nrows, N) ||
+      K < SK4_KC || K % SK4_KC || (!a_rows && a_nrows < total_rows))
+    return (int)hipErrorInvalidValue;
+  if (total_rows == 0) return 0;
+  dim3 grid((unsigned)(N / SK_NT), (unsigned)n_groups, 1);
+#define KF_SKG4_LAUNCH(MT)                                                   \
+  hipLaunchKernelGGL(kf_skinny_q4_grouped_kernel<MT>, grid,                  \
+                     dim3(SKL_W * 64), 0, (hipStream_t)stream,               \
+                     (unsigned short*)c, (const unsigned short*)a,           \
+                     (const unsigned char*)w4, wscale, offsets, a_rows,      \
+                     (int)max_rows, (int)total_rows, (int)a_nrows, N, K)
+  if (max_rows > 16) KF_SKG4_LAUNCH(32);
+  else KF_SKG4_LAUNCH(16);
   return (int)hipGetLastError();
 }

@@ -101,13 +101,19 @@ def moe_decode_mode() -> str:
     return mode
 
 
-def quantize_moe_banks(moe):
+QUANT_FORMATS = ("fp8", "mxfp4")
+
+
+def quantize_moe_banks(moe, fmt: str = "fp8"):
     """((w13_8, w13_scale), (w2_8, w2_scale)): the two expert banks of an
     MoEMLP through ops.quantize_fp8_rows on their flattened [E * out, in]
     views, one scale per (expert, output row), as
-    ops.moe_experts_decode(q8=...) takes them."""
+    ops.moe_experts_decode(q8=...) takes them. fmt="mxfp4": through
+    ops.quantize_mxfp4_rows, for its q4=."""
+    quantize = (ops.quantize_mxfp4_rows if fmt == "mxfp4"
+                else ops.quantize_fp8_rows)
     return tuple(
-        ops.quantize_fp8_rows(w.reshape(-1, w.shape[-1]))
+        quantize(w.reshape(-1, w.shape[-1]))
         for w in (moe.experts_w13, moe.experts_w2))
 
 
@@ -144,6 +150,7 @@ class InferenceEngine:
             self.max_batch = max_batch
             self.cache = None
             self.quant = False
+            self.quant_format = None
             self._qw = None
             self.use_graphs = False
             self._graphs = {}
@@ -167,34 +174,39 @@ class InferenceEngine:
         # Applied after storageUri load so trained weights quantize.
         if quant is None:
             quant = os.environ.get("KF_SERVE_QUANT", "off")
-        if quant not in ("off", "fp8"):
+        # KF_SERVE_QUANT=mxfp4: the same linears in OCP MXFP4 (W4A16, e2m1
+        # with an e8m0 scale per 32 along K), half the bytes again.
+        if quant not in ("off",) + QUANT_FORMATS:
             raise ValueError(f"unsupported quantization {quant!r} "
-                             "(supported: fp8)")
-        self.quant = quant == "fp8"
+                             f"(supported: {', '.join(QUANT_FORMATS)})")
+        self.quant = quant != "off"
+        self.quant_format = quant if self.quant else None
         self._qw = None
         moe = bool(getattr(cfg, "n_experts", 0))
-        if self.quant and moe and not self._moe_q8_usable(max_batch):
-            # the dense MoE decode has no fp8 experts: as before, such a
-            # model serves bf16 weights throughout
+        if self.quant and moe and not self._moe_quant_usable(max_batch):
+            # the dense MoE decode has no quantized experts: as before, such
+            # a model serves bf16 weights throughout
             logging.getLogger(__name__).warning(
-                "KF_SERVE_QUANT=fp8 is off for %s: its experts need the "
+                "KF_SERVE_QUANT=%s is off for %s: its experts need the "
                 "routed decode path (KF_MOE_DECODE) on a GPU, max_batch <= 32 "
                 "and hidden and ffn sizes that are multiples of 1024 (the "
-                "routed fp8 kernel's shapes)", cfg.name)
+                "routed %s kernel's shapes)", quant, cfg.name, quant)
             self.quant = False
+            self.quant_format = None
         if self.quant:
+            quantize = (ops.quantize_mxfp4_rows if quant == "mxfp4"
+                        else ops.quantize_fp8_rows)
             names = ("wqkv", "wo") if moe else ("wqkv", "wo", "w13", "w2")
             self._qw = [
-                {n: ops.quantize_fp8_rows(getattr(layer, n).weight)
-                 for n in names}
+                {n: quantize(getattr(layer, n).weight) for n in names}
                 for layer in self.model.layers
             ]
             if moe:
                 for qw, layer in zip(self._qw, self.model.layers):
-                    qw["moe"] = quantize_moe_banks(layer.moe)
+                    qw["moe"] = quantize_moe_banks(layer.moe, quant)
             # lm_head stays bf16 under "small" routing (sampling
-            # sensitivity); KF_SKINNY=all opts it into fp8 too
-            self._q_lm = ops.quantize_fp8_rows(self.model.lm_head.weight)
+            # sensitivity); KF_SKINNY=all opts it into the format too
+            self._q_lm = quantize(self.model.lm_head.weight)
         smax = min(smax, cfg.max_seq_len)
         self.cache = KVCache(cfg.n_layers, max_slots, smax,
                              cfg.n_kv_heads, cfg.head_dim, self.device, dtype)
@@ -225,16 +237,18 @@ class InferenceEngine:
         self._graphs = {}
         self._pad_slot = self.cache.alloc() if self.use_graphs else None
 
-    def _moe_q8_usable(self, max_batch: int) -> bool:
-        """fp8 experts exist only on the routed decode path: KF_MOE_DECODE
-        must select it and every layer must take it at the largest decode
-        batch (the smaller buckets then qualify too)."""
+    def _moe_quant_usable(self, max_batch: int) -> bool:
+        """Quantized experts exist only on the routed decode path:
+        KF_MOE_DECODE must select it and every layer must take it, in the
+        engine's format, at the largest decode batch (the smaller buckets then
+        qualify too)."""
         if moe_decode_mode() != "routed":
             return False
         cfg = self.model.cfg
         probe = torch.empty(max_batch, 1, cfg.hidden_size, device=self.device,
                             dtype=self.model.embed.weight.dtype)
-        return all(layer.moe.routed_decode_ok(probe, q8=True)
+        q4 = self.quant_format == "mxfp4"
+        return all(layer.moe.routed_decode_ok(probe, q8=not q4, q4=q4)
                    for layer in self.model.layers)
 
     # ------------------------------------------------------------- public
@@ -696,19 +710,20 @@ class InferenceEngine:
                "all": {"qkv", "wo", "w13", "w2", "lm"}}.get(
                    mode, set(mode.split(",")))
         qw = self._qw if self.quant else None
+        q4 = self.quant_format == "mxfp4"
+        lin_q = ops.skinny_linear_q4 if q4 else ops.skinny_linear_q8
         moe_routed = moe_decode_mode() == "routed"
 
         def _lin(name, wname):
             if qw is not None and name in sel:
-                return lambda li, t, w: ops.skinny_linear_q8(
-                    t, *qw[li][wname])
+                return lambda li, t, w: lin_q(t, *qw[li][wname])
             if name in sel:
                 return lambda li, t, w: ops.skinny_linear(t, w)
             return lambda li, t, w: F.linear(t, w)
         lin_qkv = _lin("qkv", "wqkv")
         lin_w13 = _lin("w13", "w13")
         if "lm" in sel and qw is not None:
-            lin_lm = lambda t, w: ops.skinny_linear_q8(t, *self._q_lm)
+            lin_lm = lambda t, w: lin_q(t, *self._q_lm)
         elif "lm" in sel:
             lin_lm = ops.skinny_linear
         else:
@@ -716,7 +731,7 @@ class InferenceEngine:
 
         def _lin_res(name, wname):
             if qw is not None and name in sel:
-                return lambda li, t, w, r: ops.skinny_linear_q8(
+                return lambda li, t, w, r: lin_q(
                     t, *qw[li][wname], residual=r)
             if name in sel:
                 return lambda li, t, w, r: ops.skinny_linear(
@@ -743,9 +758,10 @@ class InferenceEngine:
                        layer.wo.weight, x)  # residual fused in epilogue
             if layer.moe is not None:
                 if moe_routed:
+                    banks = qw[li]["moe"] if qw is not None else None
                     x = x + layer.moe.decode_routed(
-                        layer.mlp_norm(x),
-                        q8=qw[li]["moe"] if qw is not None else None)
+                        layer.mlp_norm(x), q8=None if q4 else banks,
+                        q4=banks if q4 else None)
                 else:
                     x = x + layer.moe.decode_dense(layer.mlp_norm(x))
             else:

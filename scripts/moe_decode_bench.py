@@ -117,6 +117,7 @@ def _rel(a, b):
 def _rows(dev, pattern, tokens, layers, window, repeats):
     mods = _modules(dev, layers, pattern)
     q8s = [quantize_moe_banks(m) for m in mods]
+    q4s = [quantize_moe_banks(m, "mxfp4") for m in mods]
     per_expert = 3 * H * FF            # w13 + w2 elements of one expert
     print(f"\nlogits: {pattern}; E{E} k{K} h{H} f{FF}, {layers} blocks per "
           "graph, times per block")
@@ -129,7 +130,8 @@ def _rows(dev, pattern, tokens, layers, window, repeats):
         x[:, :, 0] = 8.0
         x = x.to(dev, torch.bfloat16)
         for m in mods:
-            if not m.routed_decode_ok(x) or not m.routed_decode_ok(x, True):
+            if not (m.routed_decode_ok(x) and m.routed_decode_ok(x, True)
+                    and m.routed_decode_ok(x, q4=True)):
                 raise RuntimeError("routed decode does not apply; the "
                                    "comparison would be dense against dense")
         hit = []
@@ -143,6 +145,8 @@ def _rows(dev, pattern, tokens, layers, window, repeats):
             "routed": lambda: [m.decode_routed(x) for m in mods],
             "routed_fp8": lambda: [m.decode_routed(x, q8=q)
                                    for m, q in zip(mods, q8s)],
+            "routed_mxfp4": lambda: [m.decode_routed(x, q4=q)
+                                     for m, q in zip(mods, q4s)],
         }
         graphs, outs = {}, {}
         for n, fn in paths.items():
@@ -150,7 +154,7 @@ def _rows(dev, pattern, tokens, layers, window, repeats):
             graphs[n].replay()
         torch.cuda.synchronize()
         agree = {n: max(_rel(a, b) for a, b in zip(outs[n], outs["dense"]))
-                 for n in ("routed", "routed_fp8")}
+                 for n in ("routed", "routed_fp8", "routed_mxfp4")}
         times = _alternate({n: gr.replay for n, gr in graphs.items()}, window,
                            repeats)
         dense_med = _med(times["dense"]) / layers
@@ -160,6 +164,8 @@ def _rows(dev, pattern, tokens, layers, window, repeats):
             nbytes = experts * per_expert * (1 if n == "routed_fp8" else 2)
             if n == "routed_fp8":
                 nbytes += experts * (2 * FF + H) * 4  # fp32 row scales
+            if n == "routed_mxfp4":  # 4 bits and an e8m0 byte per 32
+                nbytes = experts * per_expert * (0.5 + 1 / 32)
             s = sorted(t)
             gbs = nbytes / (_med(t) * 1e-3) / 1e9
             print(f"| {T} | {n} | {_med(t) * 1e3:.1f} ({s[0] * 1e3:.1f}.."
