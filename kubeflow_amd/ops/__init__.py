@@ -40,7 +40,7 @@ __all__ = [
     "moe_experts", "moe_native_ok",
     "grouped_skinny_ok", "grouped_skinny_linear", "grouped_skinny_linear_q8",
     "grouped_skinny_linear_q4",
-    "moe_experts_decode",
+    "moe_experts_decode", "sample",
 ]
 
 rope_cos_sin = reference.rope_cos_sin
@@ -1223,6 +1223,46 @@ def attention_decode(q: torch.Tensor, kcache: torch.Tensor,
         o = reference.sdpa(qq, kk, vv, causal=False, scale=scale)
         outs.append(o.transpose(1, 2).reshape(1, Hq, D))
     return torch.cat(outs)
+
+
+# -------------------------------------------------------------- Sampling --
+
+SAMPLE_MAX_V = 1 << 22  # sample.hip: a row's fixed-point mass fits 64 bits
+
+
+def sample(logits: torch.Tensor, temperature: torch.Tensor,
+           top_k: torch.Tensor, top_p: torch.Tensor,
+           u: torch.Tensor) -> torch.Tensor:
+    """One token per row of logits [N, V] -> int32 [N] (no autograd).
+
+    Per row r: temperature[r] fp32 (<= 0: greedy, the lowest index of the
+    maximum), top_k[r] int32 (<= 0 or >= V: off), top_p[r] fp32 (>= 1: off)
+    and the uniform draw u[r] fp32 in [0, 1); the semantics are those of
+    reference.sample. bf16 logits on the GPU go to kf_sample (one launch,
+    no host sync: safe under graph capture; rows may be strided, the last
+    dim may not); anything else is computed by the reference in fp32."""
+    if logits.dim() != 2:
+        raise ValueError(
+            f"sample: logits must be [N, V], got {tuple(logits.shape)}")
+    N, V = logits.shape
+    if not (_use_native(logits) and logits.dtype == torch.bfloat16):
+        return reference.sample(logits, temperature, top_k, top_p, u)
+    lib = _backend.require()
+    if not 1 <= V < SAMPLE_MAX_V:
+        raise ValueError(f"sample: V must be in [1, {SAMPLE_MAX_V}), got {V}")
+    _index_arg("sample", "temperature", temperature, torch.float32, N, logits)
+    _index_arg("sample", "top_k", top_k, torch.int32, N, logits)
+    _index_arg("sample", "top_p", top_p, torch.float32, N, logits)
+    _index_arg("sample", "u", u, torch.float32, N, logits)
+    if logits.stride(1) != 1 or (N > 1 and logits.stride(0) < V):
+        logits = logits.contiguous()
+    stride = logits.stride(0) if N > 1 else V
+    out = torch.empty(N, dtype=torch.int32, device=logits.device)
+    _backend.check(
+        lib.kf_sample(_i32p(out), _p(logits), _fp(temperature),
+                      _i32p(top_k), _fp(top_p), _fp(u), N, V, stride,
+                      _stream()), "sample")
+    return out
 
 
 # --------------------------------------------------------- Cross entropy --

@@ -151,6 +151,8 @@ SIGNATURES: dict[str, list] = {
     "kf_moe_gather_bwd": [_P, _P, _P] + [_I64] * 4 + [_P],     # T, k, h, M
     "kf_moe_combine": [_P] * 4 + [_I64] * 4 + [_P],
     "kf_moe_combine_bwd": [_P] * 6 + [_I64] * 4 + [_P],
+    # token, logits, temperature, top_k, top_p, u, N, V, stride, stream
+    "kf_sample": [_PI32, _P, _FP, _PI32, _FP, _FP, _I64, _I64, _I64, _P],
 }
 _RETURNS_INT64 = ("kf_rmsnorm_bwd_nparts", "kf_layernorm_bwd_nparts",
                   "kf_grad_sumsq_nparts", "kf_moe_sort_nwork")

@@ -33,6 +33,14 @@ CFLAGS = [
 ]
 
 
+# Per-file additions to CFLAGS. sample.hip is built without the packed fp32
+# instructions (v_pk_add/mul/fma_f32): its tokens must not depend on how the
+# compiler pairs up the weight arithmetic.
+EXTRA_CFLAGS = {
+    "sample.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
+
+
 def _sources():
     return sorted(CSRC.glob("*.hip"))
 
@@ -78,7 +86,8 @@ def build(verbose: bool = True, force: bool = False) -> Path:
         if (obj.exists() and not force
                 and obj.stat().st_mtime > max(src.stat().st_mtime, hdr_mtime)):
             continue
-        cmd = [HIPCC, "-c", *CFLAGS, str(src), "-o", str(obj)]
+        cmd = [HIPCC, "-c", *CFLAGS, *EXTRA_CFLAGS.get(src.name, []),
+               str(src), "-o", str(obj)]
         if verbose:
             print("[kfops]", " ".join(cmd), file=sys.stderr)
         procs.append((src, subprocess.Popen(cmd, stderr=subprocess.PIPE)))

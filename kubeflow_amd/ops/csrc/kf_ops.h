@@ -208,6 +208,13 @@ KF_EXPORT int kf_moe_combine_bwd(void* dy, void* dw, const void* dout,
     const void* y, const void* topw, const void* pos, int64_t T, int64_t k,
     int64_t h, int64_t M, void* stream);
 
+// ---- sampling (sample.hip) ----
+// token int32 [N] from logits bf16 [N, V] (row stride in elements) and the
+// per-row device arrays temperature fp32, top_k int32, top_p fp32, u fp32
+KF_EXPORT int kf_sample(int* token, const void* logits,
+    const float* temperature, const int* top_k, const float* top_p,
+    const float* u, int64_t N, int64_t V, int64_t stride, void* stream);
+
 // ---- decode attention over the KV cache (attention_decode.hip) ----
 KF_EXPORT int kf_attn_decode(void* out, void* part_o, void* part_ml,
     const void* q, const void* kcache, const void* vcache, const int* slots,

@@ -233,3 +233,45 @@ def grouped_linear_offsets(x: torch.Tensor, w_bank: torch.Tensor,
         xs = x[lo:hi] if rows is None else x[rows[lo:hi].long()]
         torch.mm(xs, w_bank[e].t(), out=y[lo:hi])
     return y
+
+
+def sample(logits: torch.Tensor, temperature: torch.Tensor,
+           top_k: torch.Tensor, top_p: torch.Tensor, u: torch.Tensor,
+           dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """The reference of ops.sample, computed in `dtype`: logits [N, V],
+    per-row temperature / top_k / top_p / u [N] -> token int32 [N].
+
+    Rank order is logits descending, equal logits by ascending index (a
+    stable sort), NaN with -inf. temperature <= 0: the first entry in rank
+    order. Otherwise w = exp((x - x_max) / temperature); top_k keeps the
+    first k in rank order (k <= 0 or k >= V: off); top_p keeps the shortest
+    prefix of those whose mass is >= top_p * their mass, at least one entry
+    (top_p >= 1: off); the token is the first index, in ascending index
+    order, whose cumulative kept mass exceeds u * (kept mass): failing that
+    the last kept index of positive weight, failing that the greedy one."""
+    N, V = logits.shape
+    x = logits.to(dtype)
+    x = torch.where(torch.isnan(x), torch.full_like(x, float("-inf")), x)
+    xs, order = torch.sort(x, dim=-1, descending=True, stable=True)
+    greedy = order[:, 0]
+    t = temperature.to(dtype).unsqueeze(1)
+    sampled = (t > 0).squeeze(1)
+    w = torch.exp((xs - xs[:, :1]) / torch.where(t > 0, t, torch.ones_like(t)))
+    w = torch.where(xs == float("-inf"), torch.zeros_like(w), w)
+    pos = torch.arange(V, device=x.device).unsqueeze(0)
+    k = top_k.to(torch.int64).unsqueeze(1)
+    keep = pos < torch.where((k <= 0) | (k >= V), torch.full_like(k, V), k)
+    w = w * keep
+    cum = w.cumsum(dim=1)
+    p = top_p.to(dtype).unsqueeze(1)
+    # entry i stays while the prefix before it is still short of the target
+    w = w * ((p >= 1) | (pos == 0) | ((cum - w) < p * cum[:, -1:]))
+    wi = torch.zeros_like(w).scatter_(1, order, w)   # back to index order
+    ci = wi.cumsum(dim=1)
+    hit = ci > u.to(dtype).unsqueeze(1) * ci[:, -1:]
+    tok = (~hit).sum(dim=1)                           # hit is monotone in i
+    positive = wi > 0
+    last = (positive * pos).amax(dim=1)
+    tok = torch.where(tok < V, tok, last)
+    tok = torch.where(positive.any(dim=1) & sampled, tok, greedy)
+    return tok.to(torch.int32)

@@ -72,6 +72,9 @@ class Request:
     prompt: List[int]
     max_new_tokens: int = 32
     temperature: float = 0.0
+    top_k: int = 0            # keep the k most likely tokens; <= 0: off
+    top_p: float = 1.0        # nucleus mass; >= 1: off
+    seed: Optional[int] = None  # of this request's own draws; None: random
     submitted: float = field(default_factory=time.time)
     # filled by the engine:
     slot: int = -1
@@ -85,6 +88,23 @@ class Request:
     first_token_at: Optional[float] = None
     finished_at: Optional[float] = None
     error: str = ""
+    # the request's own CPU generator (InferenceEngine.submit) and its
+    # uniform draws, one per generated token
+    rng: Optional[torch.Generator] = field(default=None, repr=False)
+    draws: Optional[List[float]] = field(default=None, repr=False)
+
+    def next_u(self) -> float:
+        """The uniform draw of the token about to be generated: entry
+        len(generated) of one fp32 torch.rand(max_new_tokens) from the
+        request's generator, so it depends on the seed and the token's
+        position alone, not on the batch. Greedy requests draw nothing."""
+        if self.temperature <= 0:
+            return 0.0
+        if self.draws is None:
+            self.draws = torch.rand(max(1, self.max_new_tokens),
+                                    generator=self.rng,
+                                    dtype=torch.float32).tolist()
+        return self.draws[min(len(self.generated), len(self.draws) - 1)]
 
 
 def moe_decode_mode() -> str:
@@ -234,6 +254,10 @@ class InferenceEngine:
         # host sync either way, so both capture.
         self.use_graphs = (self.device.type == "cuda"
                            and os.environ.get("KF_SERVE_GRAPH", "1") == "1")
+        # KF_SAMPLE=0 (bisection): requests without top_k / top_p sample by
+        # the torch sequence (_sample_batch) on logits taken out of the
+        # graph, instead of ops.sample as the graph's last node
+        self.fused_sample = os.environ.get("KF_SAMPLE", "1") != "0"
         self._graphs = {}
         self._pad_slot = self.cache.alloc() if self.use_graphs else None
 
@@ -278,25 +302,35 @@ class InferenceEngine:
             self._thread.join(timeout=10)
 
     def submit(self, req: Request) -> Request:
+        if req.rng is None:
+            seed = (int(torch.randint(0, 2 ** 62, ()).item())
+                    if req.seed is None else int(req.seed))
+            req.rng = torch.Generator().manual_seed(seed & (2 ** 63 - 1))
         self.stats["requests"] += 1
         self.pending.put(req)
         return req
 
     def generate(self, prompt: List[int], max_new_tokens: int = 32,
-                 timeout: float = 120.0, temperature: float = 0.0) -> Request:
+                 timeout: float = 120.0, temperature: float = 0.0,
+                 top_k: int = 0, top_p: float = 1.0,
+                 seed: Optional[int] = None) -> Request:
         req = Request(rid=f"r{time.monotonic_ns()}", prompt=list(prompt),
-                      max_new_tokens=max_new_tokens, temperature=temperature)
+                      max_new_tokens=max_new_tokens, temperature=temperature,
+                      top_k=top_k, top_p=top_p, seed=seed)
         self.submit(req)
         if not req.done.wait(timeout):
             req.error = req.error or "timeout"
         return req
 
     def generate_stream(self, prompt: List[int], max_new_tokens: int = 32,
-                        temperature: float = 0.0, timeout: float = 120.0):
+                        temperature: float = 0.0, timeout: float = 120.0,
+                        top_k: int = 0, top_p: float = 1.0,
+                        seed: Optional[int] = None):
         """Submit and yield tokens as they are produced (generator)."""
         req = Request(rid=f"r{time.monotonic_ns()}", prompt=list(prompt),
                       max_new_tokens=max_new_tokens,
-                      temperature=temperature, stream=queue.Queue())
+                      temperature=temperature, top_k=top_k, top_p=top_p,
+                      seed=seed, stream=queue.Queue())
         self.submit(req)
         while True:
             try:
@@ -580,7 +614,7 @@ class InferenceEngine:
                 x = self.model.final_norm(x[:, -1:])
                 logits = torch.nn.functional.linear(
                     x, self.model.lm_head.weight)
-                tok = self._sample(logits[0, -1], req.temperature)
+                tok = self._first_tokens(logits[:, -1], [req])[0]
                 req.pos = len(prompt)
                 req.generated.append(tok)
                 req.first_token_at = time.time()
@@ -656,9 +690,9 @@ class InferenceEngine:
             x = self._layer_prefill(layer, li, x, cos, sin, slots, S)
         x = self.model.final_norm(x[:, -1:])
         logits = torch.nn.functional.linear(x, self.model.lm_head.weight)
+        toks = self._first_tokens(logits[:, -1], reqs)
         now = time.time()
-        for i, r in enumerate(reqs):
-            tok = self._sample(logits[i, -1], r.temperature)
+        for r, tok in zip(reqs, toks):
             r.pos = S
             r.generated.append(tok)
             r.first_token_at = now
@@ -694,7 +728,7 @@ class InferenceEngine:
 
     @torch.no_grad()
     def _decode_forward(self, tokens, positions, slots, lens):
-        """Batched single-token forward over the KV cache -> next tokens.
+        """Batched single-token forward over the KV cache -> logits [N,V].
         Pure function of the given (static, for graph capture) tensors."""
         cfg = self.model.cfg
         import torch.nn.functional as F
@@ -775,7 +809,7 @@ class InferenceEngine:
                 x = lin_w2(li, y, layer.w2.weight, x)
         x = self.model.final_norm(x)
         logits = lin_lm(x, self.model.lm_head.weight)  # [N,1,V]
-        return logits[:, -1]  # [N,V] (sampling happens outside the graph)
+        return logits[:, -1]  # [N,V] (_graph_for appends ops.sample)
 
     def _graph_for(self, bucket: int):
         """Capture (once) and return the decode graph for a batch bucket."""
@@ -789,18 +823,35 @@ class InferenceEngine:
                                 device=dev),
             "lens": torch.ones(bucket, dtype=torch.int32, device=dev),
         }
+        step = dict(static)
+        sampling = None
+        if self.fused_sample:
+            # per-row sampling inputs; all-zero temperature = every row greedy
+            static["temp_p"] = torch.zeros(2, bucket, device=dev)
+            static["temp_p"][1].fill_(1.0)
+            static["top_k"] = torch.zeros(bucket, dtype=torch.int32,
+                                          device=dev)
+            static["u"] = torch.zeros(bucket, device=dev)
+            static["params"] = None  # host copy of what temp_p / top_k hold
+            sampling = (static["temp_p"][0], static["top_k"],
+                        static["temp_p"][1], static["u"])
+
+        def forward():
+            """The decode step, ending in ops.sample unless KF_SAMPLE=0."""
+            logits = self._decode_forward(**step)
+            if sampling is None:
+                return logits, None
+            return logits, ops.sample(logits, *sampling)
         # warm-up on a side stream, then capture
         s = torch.cuda.Stream(device=dev)
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(2):
-                out = self._decode_forward(**static)
+                forward()
         torch.cuda.current_stream().wait_stream(s)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            static["logits"] = self._decode_forward(
-                static["tokens"], static["positions"], static["slots"],
-                static["lens"])
+            static["logits"], static["next"] = forward()
         self._graphs[bucket] = (graph, static)
         return self._graphs[bucket]
 
@@ -833,13 +884,31 @@ class InferenceEngine:
                 static["positions"][N:].zero_()
                 static["slots"][N:].fill_(self._pad_slot)
                 static["lens"][N:].fill_(1)
+            if self.fused_sample:
+                # temperature / top_p / top_k change only when the batch
+                # does, u every step unless every row is greedy; padding
+                # rows stay greedy
+                pad = bucket - N
+                params = ([r.temperature for r in acts] + [0.0] * pad,
+                          [r.top_p for r in acts] + [1.0] * pad,
+                          [r.top_k for r in acts] + [0] * pad)
+                if params != static["params"]:
+                    static["temp_p"].copy_(torch.tensor(params[:2]))
+                    static["top_k"].copy_(torch.tensor(
+                        self._clip_k(params[2]), dtype=torch.int32))
+                    static["params"] = params
+                if any(t > 0 for t in params[0]):
+                    static["u"].copy_(torch.tensor(
+                        [r.next_u() for r in acts] + [0.0] * pad))
             graph.replay()
             self.stats["graph_replays"] += 1
-            logits = static["logits"][:N]
-            toks = self._sample_batch(logits, acts)
+            if self.fused_sample:
+                toks = static["next"][:N].tolist()
+            else:
+                toks = self._sample_tokens(static["logits"][:N], acts)
         else:
             logits = self._decode_forward(tokens, positions, slots, lens)
-            toks = self._sample_batch(logits, acts)
+            toks = self._sample_tokens(logits, acts)
         still = []
         now = time.time()
         for i, r in enumerate(acts):
@@ -860,6 +929,47 @@ class InferenceEngine:
             else:
                 still.append(r)
         self.active = still
+
+    @staticmethod
+    def _clip_k(ks) -> list:
+        """top_k values as int32 can hold them (anything >= V is off)."""
+        return [min(max(int(k), 0), 2 ** 31 - 1) for k in ks]
+
+    def _sampling_args(self, reqs):
+        """(temperature, top_k, top_p, u) device tensors for ops.sample, one
+        row per request; takes each sampled request's next draw."""
+        dev = self.device
+        return (torch.tensor([r.temperature for r in reqs],
+                             dtype=torch.float32, device=dev),
+                torch.tensor(self._clip_k(r.top_k for r in reqs),
+                             dtype=torch.int32, device=dev),
+                torch.tensor([r.top_p for r in reqs], dtype=torch.float32,
+                             device=dev),
+                torch.tensor([r.next_u() for r in reqs], dtype=torch.float32,
+                             device=dev))
+
+    def _sample_tokens(self, logits: torch.Tensor, reqs,
+                       legacy=None) -> list:
+        """One token per row of logits [N,V] through ops.sample. Under
+        KF_SAMPLE=0 the requests with neither top_k nor top_p go through
+        `legacy` instead (default: _sample_batch, the torch sequence)."""
+        if self.fused_sample:
+            return ops.sample(logits, *self._sampling_args(reqs)).tolist()
+        toks = (legacy or self._sample_batch)(logits, reqs)
+        rows = [i for i, r in enumerate(reqs) if r.top_k > 0 or r.top_p < 1]
+        if rows:
+            sub = ops.sample(logits[rows],
+                             *self._sampling_args([reqs[i] for i in rows]))
+            for i, tok in zip(rows, sub.tolist()):
+                toks[i] = tok
+        return toks
+
+    def _first_tokens(self, logits: torch.Tensor, reqs) -> list:
+        """The prefill token of each request from logits [B,V]; under
+        KF_SAMPLE=0, one _sample per request as before."""
+        return self._sample_tokens(
+            logits, reqs, legacy=lambda lg, rs: [
+                self._sample(lg[i], r.temperature) for i, r in enumerate(rs)])
 
     @staticmethod
     def _sample(logits: torch.Tensor, temperature: float) -> int:

@@ -28,6 +28,17 @@ import uvicorn
 from kubeflow_amd.runtime.serving import InferenceEngine
 
 
+def _sampling_fields(body: dict) -> dict:
+    """The sampling fields of a request body as Request / generate take
+    them: temperature (0 = greedy), top_k (0 = off), top_p (1 = off) and
+    seed (absent or null = random)."""
+    seed = body.get("seed")
+    return {"temperature": float(body.get("temperature", 0.0)),
+            "top_k": int(body.get("top_k", 0)),
+            "top_p": float(body.get("top_p", 1.0)),
+            "seed": None if seed is None else int(seed)}
+
+
 def build_app(spec: dict) -> FastAPI:
     name = spec.get("name", "model")
     engine = InferenceEngine(
@@ -70,7 +81,7 @@ def build_app(spec: dict) -> FastAPI:
             r = Request(rid=f"p{time.monotonic_ns()}-{len(reqs)}",
                         prompt=list(inst.get("prompt_tokens", [1])),
                         max_new_tokens=int(inst.get("max_new_tokens", 16)),
-                        temperature=float(inst.get("temperature", 0.0)))
+                        **_sampling_fields(inst))
             engine.submit(r)
             reqs.append(r)
         preds = []
@@ -94,7 +105,7 @@ def build_app(spec: dict) -> FastAPI:
         body = await req.json()
         r = engine.generate(body.get("prompt_tokens", [1]),
                             int(body.get("max_new_tokens", 16)),
-                            temperature=float(body.get("temperature", 0.0)))
+                            **_sampling_fields(body))
         return {"tokens": r.generated, "error": r.error}
 
     @app.post(f"/v1/models/{name}:generate_stream")
@@ -108,7 +119,7 @@ def build_app(spec: dict) -> FastAPI:
         gen = engine.generate_stream(
             body.get("prompt_tokens", [1]),
             int(body.get("max_new_tokens", 16)),
-            temperature=float(body.get("temperature", 0.0)))
+            **_sampling_fields(body))
 
         async def _events():
             while True:
