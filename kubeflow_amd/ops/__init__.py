@@ -28,7 +28,7 @@ from . import _backend
 
 __all__ = [
     "rms_norm", "layer_norm", "rope", "flash_attention", "attention_decode",
-    "flash_attention_rect", "skinny_linear", "kv_store",
+    "attention_verify", "flash_attention_rect", "skinny_linear", "kv_store",
     "decode_rope_store", "skinny_linear_q8", "quantize_fp8_rows",
     "dequantize_fp8_rows", "skinny_linear_q4", "quantize_mxfp4_rows",
     "dequantize_mxfp4_rows",
@@ -1212,7 +1212,13 @@ def attention_decode(q: torch.Tensor, kcache: torch.Tensor,
                                float(scale), _stream()),
             "attn_decode")
         return out
-    # reference path: per-sequence sdpa over the cached prefix
+    return _attention_decode_ref(q, kcache, vcache, slots, lens, scale)
+
+
+def _attention_decode_ref(q, kcache, vcache, slots, lens, scale):
+    """attention_decode's reference path: per-sequence sdpa over the cached
+    prefix."""
+    N, Hq, D = q.shape
     outs = []
     for i in range(N):
         L = int(lens[i])
@@ -1223,6 +1229,52 @@ def attention_decode(q: torch.Tensor, kcache: torch.Tensor,
         o = reference.sdpa(qq, kk, vv, causal=False, scale=scale)
         outs.append(o.transpose(1, 2).reshape(1, Hq, D))
     return torch.cat(outs)
+
+
+def attention_verify(q: torch.Tensor, kcache: torch.Tensor,
+                     vcache: torch.Tensor, slots: torch.Tensor,
+                     lens: torch.Tensor, scale: Optional[float] = None):
+    """Multi-token GQA attention over the KV cache: the verify step of
+    speculative decoding (no autograd — serving).
+
+    q [N,T,Hq,D] bf16, T new tokens per sequence whose K/V rows are already
+    in the cache; kcache/vcache [SLOTS,SMAX,Hkv,D] bf16; slots/lens int32 [N].
+    lens[n] is the number of keys token 0 sees (what attention_decode takes
+    for it); token t sees t more. Returns o [N,T,Hq,D]. The native kernel
+    (kf_attn_verify) takes T <= 8 and (Hq/Hkv)*T <= 32; anything else, the
+    CPU and fp32 go row by row through attention_decode's reference path.
+    """
+    N, T, Hq, D = q.shape
+    Hkv = kcache.shape[2]
+    if scale is None:
+        scale = D ** -0.5
+    if (_use_native(q) and q.dtype == torch.bfloat16 and 1 <= T <= 8
+            and (Hq // Hkv) * T <= 32):
+        lib = _backend.require()
+        _index_arg("attention_verify", "slots", slots, torch.int32, N, q)
+        _index_arg("attention_verify", "lens", lens, torch.int32, N, q)
+        q = q.contiguous()
+        out = torch.empty_like(q)
+        # same fill-the-chip rule as attention_decode; static per (N, Hkv)
+        splits = int(os.environ.get("KF_DECODE_SPLITS", "0")) or \
+            min(8, max(1, 512 // max(1, N * Hkv)))
+        po = pm = None
+        if splits > 1:
+            po = torch.empty(N, T * Hq, splits, D, dtype=torch.float32,
+                             device=q.device)
+            pm = torch.empty(N, T * Hq, splits, 2, dtype=torch.float32,
+                             device=q.device)
+        _backend.check(
+            lib.kf_attn_verify(_p(out), _p(po), _p(pm), _p(q), _p(kcache),
+                               _p(vcache), _i32p(slots), _i32p(lens), N, T,
+                               kcache.shape[1], Hq, Hkv, D, splits,
+                               float(scale), _stream()),
+            "attn_verify")
+        return out
+    rows = (lens.view(N, 1) + torch.arange(T, device=lens.device)).reshape(-1)
+    o = _attention_decode_ref(q.reshape(N * T, Hq, D), kcache, vcache,
+                              slots.repeat_interleave(T), rows, scale)
+    return o.view(N, T, Hq, D)
 
 
 # -------------------------------------------------------------- Sampling --

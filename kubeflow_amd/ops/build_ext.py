@@ -35,9 +35,12 @@ CFLAGS = [
 
 # Per-file additions to CFLAGS. sample.hip is built without the packed fp32
 # instructions (v_pk_add/mul/fma_f32): its tokens must not depend on how the
-# compiler pairs up the weight arithmetic.
+# compiler pairs up the weight arithmetic. attention_verify.hip likewise:
+# the accepted tokens of a verify step must not depend on that pairing.
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_CFLAGS = {
-    "sample.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "sample.hip": _NO_PK_F32,
+    "attention_verify.hip": _NO_PK_F32,
 }
 
 

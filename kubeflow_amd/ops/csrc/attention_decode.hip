@@ -234,6 +234,16 @@ __global__ __launch_bounds__(64) void kf_attn_decode_combine_kernel(
   out[row * AD_D + lane * 2 + 1] = kf_f32_to_bf16(o1 * inv_l);
 }
 
+// the combine for partials written by another file's kernel
+// (attention_verify.hip): rows = number of [splits,128] partial groups
+void kf_attn_decode_combine_launch(void* out, const void* part_o,
+                                   const void* part_ml, int64_t rows,
+                                   int splits, void* stream) {
+  hipLaunchKernelGGL(kf_attn_decode_combine_kernel, dim3((unsigned)rows),
+                     dim3(64), 0, (hipStream_t)stream, (unsigned short*)out,
+                     (const float*)part_o, (const float*)part_ml, splits);
+}
+
 // splits > 1 requires part_o [N,Hq,splits,128] f32 and part_ml
 // [N,Hq,splits,2] f32 workspaces; pass splits = 0 to let the host pick
 // enough grid.z to fill the chip (2 blocks/CU).

@@ -17,6 +17,12 @@ typedef float kf_f32x4 __attribute__((ext_vector_type(4)));
 typedef float kf_f32x16 __attribute__((ext_vector_type(16)));
 // (kf_short4 / kf_short8 come from kf_common.h)
 
+// attention_decode.hip's split-partial combine, for attention_verify.hip
+// (library-internal: not an exported entry point)
+void kf_attn_decode_combine_launch(void* out, const void* part_o,
+                                   const void* part_ml, int64_t rows,
+                                   int splits, void* stream);
+
 #define KF_LOG2E 1.44269504f
 #define KF_LN2 0.69314718f
 #define KF_DEFER_MAX_THR2 11.5415603f  // 8 * log2(e): defer-max, exp2 units

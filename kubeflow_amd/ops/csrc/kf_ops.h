@@ -220,3 +220,10 @@ KF_EXPORT int kf_attn_decode(void* out, void* part_o, void* part_ml,
     const void* q, const void* kcache, const void* vcache, const int* slots,
     const int* lens, int64_t N, int64_t smax, int64_t Hq, int64_t Hkv,
     int64_t D, int64_t splits, float scale, void* stream);
+
+// ---- multi-token verify attention over the KV cache (attention_verify.hip)
+// q/out [N, T, Hq, 128]; lens[n] = keys visible to token 0, token t sees t more
+KF_EXPORT int kf_attn_verify(void* out, void* part_o, void* part_ml,
+    const void* q, const void* kcache, const void* vcache, const int* slots,
+    const int* lens, int64_t N, int64_t T, int64_t smax, int64_t Hq,
+    int64_t Hkv, int64_t D, int64_t splits, float scale, void* stream);

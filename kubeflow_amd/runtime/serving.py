@@ -98,13 +98,34 @@ class Request:
         len(generated) of one fp32 torch.rand(max_new_tokens) from the
         request's generator, so it depends on the seed and the token's
         position alone, not on the batch. Greedy requests draw nothing."""
+        return self.u_at(len(self.generated))
+
+    def u_at(self, i: int) -> float:
+        """The uniform draw of generated token i. Draws are indexed by token,
+        not consumed per step: a verify step reads several of them and the
+        ones behind a rejected draft are read again by the next step."""
         if self.temperature <= 0:
             return 0.0
         if self.draws is None:
             self.draws = torch.rand(max(1, self.max_new_tokens),
                                     generator=self.rng,
                                     dtype=torch.float32).tolist()
-        return self.draws[min(len(self.generated), len(self.draws) - 1)]
+        return self.draws[min(i, len(self.draws) - 1)]
+
+
+def draft_tokens(history: List[int], k: int, max_ngram: int = 3) -> List[int]:
+    """Prompt-lookup draft: the k tokens that followed the most recent
+    earlier occurrence of the longest suffix of `history` (up to max_ngram
+    tokens) that occurs earlier in it. Positions with no proposal carry
+    token 0. Any draft is valid: a wrong one is simply rejected."""
+    n_hist = len(history)
+    for n in range(min(max_ngram, n_hist - 1), 0, -1):
+        suffix = history[-n:]
+        for i in range(n_hist - n - 1, -1, -1):
+            if history[i:i + n] == suffix:
+                follow = list(history[i + n:i + n + k])
+                return follow + [0] * (k - len(follow))
+    return [0] * k
 
 
 def moe_decode_mode() -> str:
@@ -243,7 +264,16 @@ class InferenceEngine:
         self._stop = False
         self._thread: Optional[threading.Thread] = None
         self.stats = {"requests": 0, "completed": 0, "tokens_out": 0,
-                      "prefill_tokens": 0, "graph_replays": 0}
+                      "prefill_tokens": 0, "graph_replays": 0,
+                      "spec_steps": 0, "spec_proposed": 0, "spec_accepted": 0}
+        # KF_SPEC_TOKENS=k: speculative decoding with k prompt-lookup draft
+        # tokens per sequence, verified in one step of k + 1 rows per
+        # sequence (_verify_step). 0: off, the one-token step only.
+        self.spec_tokens = int(os.environ.get("KF_SPEC_TOKENS", "0"))
+        if not 0 <= self.spec_tokens <= 7:
+            raise ValueError("KF_SPEC_TOKENS must be in 0..7 (a verify step "
+                             "is at most 8 tokens per sequence), got "
+                             f"{self.spec_tokens}")
         # hipGraph decode: capture the whole batched decode step per batch
         # bucket (the ~10 kernels x 32 layers of launch overhead dominate
         # small-batch decode latency otherwise). One cache slot is reserved
@@ -288,6 +318,8 @@ class InferenceEngine:
             b = 1
             while True:
                 self._graph_for(b)
+                if self.spec_tokens and b * (self.spec_tokens + 1) <= 32:
+                    self._graph_for(b, self.spec_tokens + 1)
                 if b >= self.max_batch:
                     break
                 b = min(b * 2, self.max_batch)
@@ -727,9 +759,13 @@ class InferenceEngine:
         return x + layer.w2(torch.nn.functional.silu(g) * u)
 
     @torch.no_grad()
-    def _decode_forward(self, tokens, positions, slots, lens):
+    def _decode_forward(self, tokens, positions, slots, lens, T=1,
+                        seq_slots=None):
         """Batched single-token forward over the KV cache -> logits [N,V].
-        Pure function of the given (static, for graph capture) tensors."""
+        Pure function of the given (static, for graph capture) tensors.
+        T > 1 (verify step): the N rows are T consecutive tokens of each of
+        N / T sequences, positions and slots per row, lens and seq_slots per
+        sequence, lens the keys visible to a sequence's first row."""
         cfg = self.model.cfg
         import torch.nn.functional as F
         N = tokens.shape[0]
@@ -786,8 +822,13 @@ class InferenceEngine:
                                       self.cache.v[li], cos, sin, slots,
                                       positions, cfg.n_heads,
                                       cfg.n_kv_heads)
-            o = ops.attention_decode(q, self.cache.k[li],
-                                     self.cache.v[li], slots, lens)
+            if T == 1:
+                o = ops.attention_decode(q, self.cache.k[li],
+                                         self.cache.v[li], slots, lens)
+            else:
+                o = ops.attention_verify(
+                    q.view(N // T, T, cfg.n_heads, cfg.head_dim),
+                    self.cache.k[li], self.cache.v[li], seq_slots, lens)
             x = lin_wo(li, o.reshape(N, 1, cfg.n_heads * cfg.head_dim),
                        layer.wo.weight, x)  # residual fused in epilogue
             if layer.moe is not None:
@@ -811,27 +852,35 @@ class InferenceEngine:
         logits = lin_lm(x, self.model.lm_head.weight)  # [N,1,V]
         return logits[:, -1]  # [N,V] (_graph_for appends ops.sample)
 
-    def _graph_for(self, bucket: int):
-        """Capture (once) and return the decode graph for a batch bucket."""
-        if bucket in self._graphs:
-            return self._graphs[bucket]
+    def _graph_for(self, bucket: int, T: int = 1):
+        """Capture (once) and return the decode graph for a batch bucket: the
+        one-token step (key `bucket`), or the verify step of T tokens per
+        sequence (key `(bucket, T)`, bucket * T rows). Every row starts parked
+        on the padding slot, a sequence's rows at positions 0..T-1."""
+        key = bucket if T == 1 else (bucket, T)
+        if key in self._graphs:
+            return self._graphs[key]
         dev = self.device
+        rows = bucket * T
         static = {
-            "tokens": torch.zeros(bucket, 1, dtype=torch.int64, device=dev),
-            "positions": torch.zeros(bucket, dtype=torch.int64, device=dev),
-            "slots": torch.full((bucket,), self._pad_slot, dtype=torch.int32,
+            "tokens": torch.zeros(rows, 1, dtype=torch.int64, device=dev),
+            "positions": torch.arange(T, device=dev).repeat(bucket),
+            "slots": torch.full((rows,), self._pad_slot, dtype=torch.int32,
                                 device=dev),
             "lens": torch.ones(bucket, dtype=torch.int32, device=dev),
         }
-        step = dict(static)
+        if T > 1:
+            static["seq_slots"] = torch.full((bucket,), self._pad_slot,
+                                             dtype=torch.int32, device=dev)
+        step = dict(static, T=T) if T > 1 else dict(static)
         sampling = None
         if self.fused_sample:
             # per-row sampling inputs; all-zero temperature = every row greedy
-            static["temp_p"] = torch.zeros(2, bucket, device=dev)
+            static["temp_p"] = torch.zeros(2, rows, device=dev)
             static["temp_p"][1].fill_(1.0)
-            static["top_k"] = torch.zeros(bucket, dtype=torch.int32,
+            static["top_k"] = torch.zeros(rows, dtype=torch.int32,
                                           device=dev)
-            static["u"] = torch.zeros(bucket, device=dev)
+            static["u"] = torch.zeros(rows, device=dev)
             static["params"] = None  # host copy of what temp_p / top_k hold
             sampling = (static["temp_p"][0], static["top_k"],
                         static["temp_p"][1], static["u"])
@@ -852,8 +901,8 @@ class InferenceEngine:
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             static["logits"], static["next"] = forward()
-        self._graphs[bucket] = (graph, static)
-        return self._graphs[bucket]
+        self._graphs[key] = (graph, static)
+        return self._graphs[key]
 
     @torch.no_grad()
     def _decode_step(self):
@@ -861,6 +910,10 @@ class InferenceEngine:
         GPU; eager on CPU)."""
         acts = self.active
         N = len(acts)
+        T = self.spec_tokens + 1
+        if (T > 1 and N * T <= 32
+                and all(r.pos + T <= self.cache.smax for r in acts)):
+            return self._verify_step(T)
         tokens = torch.tensor([[r.generated[-1]] for r in acts],
                               dtype=torch.int64, device=self.device)
         positions = torch.tensor([r.pos for r in acts], dtype=torch.int64,
@@ -909,24 +962,112 @@ class InferenceEngine:
         else:
             logits = self._decode_forward(tokens, positions, slots, lens)
             toks = self._sample_tokens(logits, acts)
-        still = []
         now = time.time()
-        for i, r in enumerate(acts):
-            r.pos += 1
-            r.generated.append(int(toks[i]))
-            r.token_times.append(now)
+        self.active = [r for i, r in enumerate(acts)
+                       if not self._emit(r, int(toks[i]), now)]
+
+    def _emit(self, r: Request, tok: int, now: float) -> bool:
+        """Append one generated token to r; True if that finished it."""
+        # A verify step wrote cache rows pos .. pos+T-1, and the rows of
+        # rejected drafts lie at positions >= the new pos. No row sees them:
+        # a step's rows see keys < their own position + 1 only, and it first
+        # rewrites every row from pos up to the last one it reads.
+        r.pos += 1
+        r.generated.append(tok)
+        r.token_times.append(now)
+        if r.stream is not None:
+            r.stream.put(tok)
+        self.stats["tokens_out"] += 1
+        if (len(r.generated) >= r.max_new_tokens
+                or r.pos + 1 >= self.cache.smax):
+            r.finished_at = now
+            self._finish_slot(r)
+            self.stats["completed"] += 1
             if r.stream is not None:
-                r.stream.put(int(toks[i]))
-            self.stats["tokens_out"] += 1
-            if (len(r.generated) >= r.max_new_tokens
-                    or r.pos + 1 >= self.cache.smax):
-                r.finished_at = now
-                self._finish_slot(r)
-                self.stats["completed"] += 1
-                if r.stream is not None:
-                    r.stream.put(None)
-                r.done.set()
+                r.stream.put(None)
+            r.done.set()
+            return True
+        return False
+
+    @torch.no_grad()
+    def _verify_step(self, T: int):
+        """One speculative step: T = k + 1 rows per active sequence, its last
+        token and k prompt-lookup drafts, through one forward. Acceptance is
+        sample-and-match: row t is sampled from its own logits with the
+        request's parameters and the draw of generated token
+        len(generated) + t; token 0 is emitted, and token i + 1 while draft
+        i + 1 equals token i. Exact for drafts that do not depend on the
+        draws: every emitted token is what the one-token step would have
+        sampled after the same history."""
+        acts = self.active
+        N, k, dev = len(acts), T - 1, self.device
+        drafts = [draft_tokens(r.prompt + r.generated, k) for r in acts]
+        rows = [r for r in acts for _ in range(T)]  # the request of each row
+        tokens = torch.tensor(
+            [[t] for r, d in zip(acts, drafts) for t in [r.generated[-1]] + d],
+            dtype=torch.int64, device=dev)
+        positions = torch.tensor([r.pos + t for r in acts for t in range(T)],
+                                 dtype=torch.int64, device=dev)
+        seq_slots = torch.tensor([r.slot for r in acts], dtype=torch.int32,
+                                 device=dev)
+        slots = seq_slots.repeat_interleave(T)
+        lens = torch.tensor([r.pos + 1 for r in acts], dtype=torch.int32,
+                            device=dev)
+        us = [r.u_at(len(r.generated) + t) for r in acts for t in range(T)]
+        if self.use_graphs:
+            bucket = 1
+            while bucket < N:
+                bucket *= 2
+            bucket = min(bucket, self.max_batch, 32 // T)
+            graph, static = self._graph_for(bucket, T)
+            R = N * T
+            static["tokens"][:R].copy_(tokens)
+            static["positions"][:R].copy_(positions)
+            static["slots"][:R].copy_(slots)
+            static["seq_slots"][:N].copy_(seq_slots)
+            static["lens"][:N].copy_(lens)
+            if bucket > N:  # park padding rows on the reserved slot
+                static["tokens"][R:].zero_()
+                static["positions"][R:].copy_(
+                    torch.arange(T, device=dev).repeat(bucket - N))
+                static["slots"][R:].fill_(self._pad_slot)
+                static["seq_slots"][N:].fill_(self._pad_slot)
+                static["lens"][N:].fill_(1)
+            if self.fused_sample:
+                pad = bucket * T - R
+                params = ([r.temperature for r in rows] + [0.0] * pad,
+                          [r.top_p for r in rows] + [1.0] * pad,
+                          [r.top_k for r in rows] + [0] * pad)
+                if params != static["params"]:
+                    static["temp_p"].copy_(torch.tensor(params[:2]))
+                    static["top_k"].copy_(torch.tensor(
+                        self._clip_k(params[2]), dtype=torch.int32))
+                    static["params"] = params
+                if any(t > 0 for t in params[0]):
+                    static["u"].copy_(torch.tensor(us + [0.0] * pad))
+            graph.replay()
+            self.stats["graph_replays"] += 1
+            if self.fused_sample:
+                toks = static["next"][:R].tolist()
             else:
+                toks = self._sample_tokens(static["logits"][:R], rows, us=us)
+        else:
+            logits = self._decode_forward(tokens, positions, slots, lens, T,
+                                          seq_slots)
+            toks = self._sample_tokens(logits, rows, us=us)
+        now = time.time()
+        self.stats["spec_steps"] += 1
+        self.stats["spec_proposed"] += N * k
+        still = []
+        for i, (r, d) in enumerate(zip(acts, drafts)):
+            row = toks[i * T:(i + 1) * T]
+            done = self._emit(r, int(row[0]), now)
+            j = 0
+            while not done and j < k and d[j] == row[j]:
+                j += 1
+                done = self._emit(r, int(row[j]), now)
+                self.stats["spec_accepted"] += 1
+            if not done:
                 still.append(r)
         self.active = still
 
@@ -935,9 +1076,10 @@ class InferenceEngine:
         """top_k values as int32 can hold them (anything >= V is off)."""
         return [min(max(int(k), 0), 2 ** 31 - 1) for k in ks]
 
-    def _sampling_args(self, reqs):
+    def _sampling_args(self, reqs, us=None):
         """(temperature, top_k, top_p, u) device tensors for ops.sample, one
-        row per request; takes each sampled request's next draw."""
+        row per request; takes each sampled request's next draw, or the
+        draws `us` (a verify step's, one per row)."""
         dev = self.device
         return (torch.tensor([r.temperature for r in reqs],
                              dtype=torch.float32, device=dev),
@@ -945,21 +1087,23 @@ class InferenceEngine:
                              dtype=torch.int32, device=dev),
                 torch.tensor([r.top_p for r in reqs], dtype=torch.float32,
                              device=dev),
-                torch.tensor([r.next_u() for r in reqs], dtype=torch.float32,
-                             device=dev))
+                torch.tensor([r.next_u() for r in reqs] if us is None else us,
+                             dtype=torch.float32, device=dev))
 
     def _sample_tokens(self, logits: torch.Tensor, reqs,
-                       legacy=None) -> list:
+                       legacy=None, us=None) -> list:
         """One token per row of logits [N,V] through ops.sample. Under
         KF_SAMPLE=0 the requests with neither top_k nor top_p go through
         `legacy` instead (default: _sample_batch, the torch sequence)."""
         if self.fused_sample:
-            return ops.sample(logits, *self._sampling_args(reqs)).tolist()
+            return ops.sample(logits,
+                              *self._sampling_args(reqs, us)).tolist()
         toks = (legacy or self._sample_batch)(logits, reqs)
         rows = [i for i, r in enumerate(reqs) if r.top_k > 0 or r.top_p < 1]
         if rows:
-            sub = ops.sample(logits[rows],
-                             *self._sampling_args([reqs[i] for i in rows]))
+            sub = ops.sample(logits[rows], *self._sampling_args(
+                [reqs[i] for i in rows],
+                None if us is None else [us[i] for i in rows]))
             for i, tok in zip(rows, sub.tolist()):
                 toks[i] = tok
         return toks
