@@ -28,7 +28,8 @@ from . import _backend
 
 __all__ = [
     "rms_norm", "layer_norm", "rope", "flash_attention", "attention_decode",
-    "attention_verify", "flash_attention_rect", "skinny_linear", "kv_store",
+    "attention_verify", "attention_prefill", "flash_attention_rect",
+    "skinny_linear", "kv_store",
     "decode_rope_store", "skinny_linear_q8", "quantize_fp8_rows",
     "dequantize_fp8_rows", "skinny_linear_q4", "quantize_mxfp4_rows",
     "dequantize_mxfp4_rows",
@@ -1275,6 +1276,63 @@ def attention_verify(q: torch.Tensor, kcache: torch.Tensor,
     o = _attention_decode_ref(q.reshape(N * T, Hq, D), kcache, vcache,
                               slots.repeat_interleave(T), rows, scale)
     return o.view(N, T, Hq, D)
+
+
+def attention_prefill(q: torch.Tensor, kcache: torch.Tensor,
+                      vcache: torch.Tensor, slots: torch.Tensor,
+                      starts: torch.Tensor, lens: torch.Tensor, max_rows: int,
+                      scale: Optional[float] = None):
+    """Ragged batched prefill GQA attention over the KV cache (no autograd —
+    serving).
+
+    q [R,Hq,D] bf16: the packed query rows of N sequences. Rows
+    [starts[n], starts[n+1]) are consecutive tokens of sequence n, whose K/V
+    rows are already in cache slot slots[n]; lens[n] is the number of keys its
+    token 0 sees (attention_verify's convention), token i sees i more.
+    kcache/vcache [SLOTS,SMAX,Hkv,D] bf16; slots/lens int32 [N], starts int32
+    [N+1]. max_rows is a host bound on any sequence's row count (it sizes the
+    grid; rows past it are not computed). Returns o [R,Hq,D]; rows outside
+    every range are left unwritten. The three index tensors are read on the
+    device only, so a captured call follows their contents. The CPU, fp32 and
+    D != 128 expand the rows on the host and go through attention_decode's
+    reference path.
+    """
+    R, Hq, D = q.shape
+    N = slots.shape[0] if isinstance(slots, torch.Tensor) else 0
+    Hkv = kcache.shape[2]
+    if scale is None:
+        scale = D ** -0.5
+    if (_use_native(q) and q.dtype == torch.bfloat16 and D == 128
+            and Hq // Hkv in (1, 2, 4, 8)):
+        lib = _backend.require()
+        _index_arg("attention_prefill", "slots", slots, torch.int32, N, q)
+        _index_arg("attention_prefill", "starts", starts, torch.int32, N + 1,
+                   q)
+        _index_arg("attention_prefill", "lens", lens, torch.int32, N, q)
+        q = q.contiguous()
+        out = torch.empty_like(q)
+        _backend.check(
+            lib.kf_attn_prefill(_p(out), _p(q), _p(kcache), _p(vcache),
+                                _i32p(slots), _i32p(starts), _i32p(lens), N,
+                                R, int(max_rows), kcache.shape[1],
+                                kcache.shape[0], Hq, Hkv, D, float(scale),
+                                _stream()),
+            "attn_prefill")
+        return out
+    st = starts.tolist()
+    out = torch.zeros_like(q)
+    for n in range(N):
+        c = min(st[n + 1] - st[n], int(max_rows))
+        l0 = max(int(lens[n]), 0)
+        z = 1 if l0 == 0 else 0          # a row with no key stays zero
+        if c <= z:
+            continue
+        vis = (l0 + torch.arange(z, c, device=lens.device)) \
+            .clamp(max=kcache.shape[1])
+        out[st[n] + z:st[n] + c] = _attention_decode_ref(
+            q[st[n] + z:st[n] + c], kcache, vcache, slots[n].repeat(c - z),
+            vis, scale)
+    return out
 
 
 # -------------------------------------------------------------- Sampling --

@@ -36,11 +36,13 @@ CFLAGS = [
 # Per-file additions to CFLAGS. sample.hip is built without the packed fp32
 # instructions (v_pk_add/mul/fma_f32): its tokens must not depend on how the
 # compiler pairs up the weight arithmetic. attention_verify.hip likewise:
-# the accepted tokens of a verify step must not depend on that pairing.
+# the accepted tokens of a verify step must not depend on that pairing, nor
+# the first tokens that attention_prefill.hip's rows lead to.
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_CFLAGS = {
     "sample.hip": _NO_PK_F32,
     "attention_verify.hip": _NO_PK_F32,
+    "attention_prefill.hip": _NO_PK_F32,
 }
 
 

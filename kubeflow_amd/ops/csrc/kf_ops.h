@@ -227,3 +227,11 @@ KF_EXPORT int kf_attn_verify(void* out, void* part_o, void* part_ml,
     const void* q, const void* kcache, const void* vcache, const int* slots,
     const int* lens, int64_t N, int64_t T, int64_t smax, int64_t Hq,
     int64_t Hkv, int64_t D, int64_t splits, float scale, void* stream);
+
+// ---- ragged prefill attention over the KV cache (attention_prefill.hip)
+// q/out [R, Hq, 128] packed rows; rows [starts[n], starts[n+1]) are sequence
+// n's tokens, lens[n] = keys visible to its token 0; max_rows bounds any C_n
+KF_EXPORT int kf_attn_prefill(void* out, const void* q, const void* kcache,
+    const void* vcache, const int* slots, const int* starts, const int* lens,
+    int64_t N, int64_t R, int64_t max_rows, int64_t smax, int64_t n_slots,
+    int64_t Hq, int64_t Hkv, int64_t D, float scale, void* stream);

@@ -288,6 +288,12 @@ class InferenceEngine:
         # the torch sequence (_sample_batch) on logits taken out of the
         # graph, instead of ops.sample as the graph's last node
         self.fused_sample = os.environ.get("KF_SAMPLE", "1") != "0"
+        # KF_PREFILL_RAGGED=1: mixed-length prompts prefill as one packed
+        # forward over ops.attention_prefill (_prefill_ragged), and chunks /
+        # prefix-cache tails go through it too. Off by default: llama3-8b
+        # serving is 3-4% faster on mixed lengths but 5-7% slower on equal
+        # ones, which already batch (profiles/prefill_ragged.md).
+        self.prefill_ragged = os.environ.get("KF_PREFILL_RAGGED", "0") != "0"
         self._graphs = {}
         self._pad_slot = self.cache.alloc() if self.use_graphs else None
 
@@ -480,7 +486,10 @@ class InferenceEngine:
             group = self._take_prefill_group()
             if group:
                 try:
-                    self._prefill_many(group)
+                    if self.prefill_ragged:
+                        self._prefill_ragged(group)
+                    else:
+                        self._prefill_many(group)
                     self.active.extend(group)
                 except Exception as e:  # pragma: no cover
                     import traceback
@@ -517,7 +526,9 @@ class InferenceEngine:
         length matches the head request's; requeue mismatches (slight
         reorder — a scheduler decision, not a protocol one). Returns []
         when batching does not apply (it needs >=2 same-length prompts,
-        free slots, and an inline-size prompt)."""
+        free slots, and an inline-size prompt). With prefill_ragged the
+        lengths may differ (_prefill_ragged packs them) and the group's
+        total rows stay within PREFILL_CHUNK."""
         if self.PREFILL_GROUP < 2:
             return []
 
@@ -525,7 +536,7 @@ class InferenceEngine:
             return len(r.prompt[-max(1, self.cache.smax
                                      - r.max_new_tokens - 1):])
 
-        taken, back = [], []
+        taken, back, rows = [], [], 0
         while len(taken) < self.PREFILL_GROUP:
             try:
                 r = self.pending.get_nowait()
@@ -533,9 +544,16 @@ class InferenceEngine:
                 break
             if not taken:
                 taken.append(r)
+                rows = eff_len(r)
                 continue
-            if eff_len(r) == eff_len(taken[0]):
+            if self.prefill_ragged:
+                # any lengths batch; the packed rows are capped at one chunk
+                ok = rows + eff_len(r) <= self.PREFILL_CHUNK
+            else:
+                ok = eff_len(r) == eff_len(taken[0])
+            if ok:
                 taken.append(r)
+                rows += eff_len(r)
             else:
                 back.append(r)
         for r in back:
@@ -671,7 +689,10 @@ class InferenceEngine:
     def _prefill_chunk(self, req: Request, chunk, pos: int):
         """One CHUNK-token slice through all layers: cache rows
         [pos, pos+C) fill and the chunk attends the whole prefix via the
-        rectangular-causal kernel."""
+        rectangular-causal kernel — or, with prefill_ragged, as a one-
+        sequence ragged forward: no 256-row pad and no slab view."""
+        if self.prefill_ragged:
+            return self._ragged_hidden([chunk], [req.slot], [pos])[0]
         cfg = self.model.cfg
         C = len(chunk)
         import torch.nn.functional as F
@@ -702,6 +723,81 @@ class InferenceEngine:
                     [cfg.ffn_dim, cfg.ffn_dim], dim=-1)
                 x = x + layer.w2(F.silu(g) * u)
         return x
+
+    @torch.no_grad()
+    def _ragged_hidden(self, chunks, slots, pos0):
+        """One packed [1, R, h] forward over token chunks of several
+        sequences, any length each: chunk n goes to cache rows
+        [pos0[n], pos0[n] + len) of slot slots[n] and attends its slot's
+        whole prefix. Per layer the fused QKV rows go through
+        ops.decode_rope_store (per-row slot and position: RoPE plus the
+        cache write, no per-request slice assignment) and
+        ops.attention_prefill reads K/V in place. Returns the hidden rows
+        [1, R, h] and each chunk's last row index."""
+        cfg = self.model.cfg
+        import torch.nn.functional as F
+        counts = [len(c) for c in chunks]
+        R = sum(counts)
+        starts = [0]
+        for c in counts:
+            starts.append(starts[-1] + c)
+        dev = self.device
+        tokens = torch.tensor([[t for c in chunks for t in c]],
+                              dtype=torch.int64, device=dev)
+        positions = torch.tensor(
+            [p + i for c, p in zip(counts, pos0) for i in range(c)],
+            dtype=torch.int64, device=dev)
+        row_slots = torch.tensor(
+            [s for c, s in zip(counts, slots) for _ in range(c)],
+            dtype=torch.int32, device=dev)
+        seq_slots = torch.tensor(slots, dtype=torch.int32, device=dev)
+        starts_t = torch.tensor(starts, dtype=torch.int32, device=dev)
+        # keys visible to a chunk's first token: its prefix and itself
+        lens = torch.tensor([p + 1 for p in pos0], dtype=torch.int32,
+                            device=dev)
+        x = self.model.embed(tokens)
+        cos, sin = self.model.rope_cos, self.model.rope_sin
+        for li, layer in enumerate(self.model.layers):
+            qkv = F.linear(layer.attn_norm(x), layer.wqkv.weight)
+            q = ops.decode_rope_store(qkv[0], self.cache.k[li],
+                                      self.cache.v[li], cos, sin, row_slots,
+                                      positions, cfg.n_heads, cfg.n_kv_heads)
+            o = ops.attention_prefill(q, self.cache.k[li], self.cache.v[li],
+                                      seq_slots, starts_t, lens, max(counts),
+                                      scale=cfg.head_dim ** -0.5)
+            x = x + layer.wo(o.reshape(1, R, cfg.n_heads * cfg.head_dim))
+            if layer.moe is not None:
+                x = x + layer.moe(layer.mlp_norm(x))
+            else:
+                g, u = F.linear(layer.mlp_norm(x), layer.w13.weight).split(
+                    [cfg.ffn_dim, cfg.ffn_dim], dim=-1)
+                x = x + layer.w2(F.silu(g) * u)
+        return x, [s - 1 for s in starts[1:]]
+
+    @torch.no_grad()
+    def _prefill_ragged(self, reqs):
+        """Prefill prompts of any lengths as one packed forward
+        (_ragged_hidden), fill each request's cache slot and produce its
+        first token; final_norm and lm_head run on the last rows only.
+        Returns those rows' logits [N, V]."""
+        keep = [max(1, self.cache.smax - r.max_new_tokens - 1) for r in reqs]
+        prompts = [r.prompt[-k:] for r, k in zip(reqs, keep)]
+        x, last = self._ragged_hidden(prompts, [r.slot for r in reqs],
+                                      [0] * len(reqs))
+        x = self.model.final_norm(x[0, last].unsqueeze(1))      # [N,1,h]
+        logits = torch.nn.functional.linear(
+            x, self.model.lm_head.weight)[:, -1]
+        toks = self._first_tokens(logits, reqs)
+        now = time.time()
+        for r, p, tok in zip(reqs, prompts, toks):
+            r.pos = len(p)
+            r.generated.append(tok)
+            r.first_token_at = now
+            r.token_times.append(now)
+            if r.stream is not None:
+                r.stream.put(tok)
+            self.stats["prefill_tokens"] += len(p)
+        return logits
 
     @torch.no_grad()
     def _prefill(self, req: Request):
