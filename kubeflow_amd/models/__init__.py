@@ -7,8 +7,8 @@ from __future__ import annotations
 from typing import Callable, Dict
 
 from .llama import (LlamaConfig, LlamaModel, llama3_8b, llama3_1b,
-                    llama3_70b, llama_moe_3b, llama_moe_tiny, llama_tiny,
-                    llama_tiny_mha)
+                    llama3_2_1b, llama3_70b, llama_moe_3b, llama_moe_tiny,
+                    llama_tiny, llama_tiny_d64, llama_tiny_mha)
 from .bert import (BertConfig, BertClassifier, bert_base, bert_base_hd128,
                    bert_tiny)
 from .mlp import MnistMLP
@@ -48,8 +48,10 @@ def _mlp(device=None, dtype=None, **kw):
 MODEL_CONFIGS: Dict[str, Callable] = {
     "llama3-8b": llama3_8b,
     "llama3-1b": llama3_1b,
+    "llama3.2-1b": llama3_2_1b,
     "llama3-70b": llama3_70b,
     "llama-tiny": llama_tiny,
+    "llama-tiny-d64": llama_tiny_d64,
     "llama-tiny-mha": llama_tiny_mha,
     "llama-moe-tiny": llama_moe_tiny,
     "llama-moe-3b": llama_moe_3b,
@@ -70,8 +72,10 @@ def model_config(name: str):
 MODEL_REGISTRY: Dict[str, Callable] = {
     "llama3-8b": _llama(llama3_8b),
     "llama3-1b": _llama(llama3_1b),
+    "llama3.2-1b": _llama(llama3_2_1b),
     "llama3-70b": _llama(llama3_70b),
     "llama-tiny": _llama(llama_tiny),
+    "llama-tiny-d64": _llama(llama_tiny_d64),
     "llama-tiny-mha": _llama(llama_tiny_mha),
     "llama-moe-tiny": _llama(llama_moe_tiny),
     "llama-moe-3b": _llama(llama_moe_3b),

@@ -59,9 +59,23 @@ def llama3_8b() -> LlamaConfig:
 
 
 def llama3_1b() -> LlamaConfig:
-    """Scaled-down config for quick GPU smoke/bench runs."""
+    """Scaled-down config for quick GPU smoke/bench runs: a head-dim-128
+    stand-in, not a published shape (see llama3_2_1b for that)."""
     return LlamaConfig(name="llama3-1b", hidden_size=2048, n_layers=16,
                        n_heads=16, n_kv_heads=8, ffn_dim=8192)
+
+
+def llama3_2_1b() -> LlamaConfig:
+    """The Llama-3.2-1B shape: 32 q-heads and 8 kv-heads of head dim 64.
+    Serving runs on the D = 64 cache-attention kernel (kf_attn64_cache).
+    Not modelled: the tied input/output embeddings (lm_head is its own
+    matrix here, so n_params counts it twice over the published 1.24B) and
+    the rope frequency scaling for contexts beyond 8k (max_seq_len stays
+    8192, plain theta-500000 rope)."""
+    return LlamaConfig(name="llama3.2-1b", hidden_size=2048, n_layers=16,
+                       n_heads=32, n_kv_heads=8, head_dim=64, ffn_dim=8192,
+                       vocab_size=128256, rope_theta=500000.0,
+                       max_seq_len=8192)
 
 
 def llama3_70b() -> LlamaConfig:
@@ -76,10 +90,19 @@ def llama3_70b() -> LlamaConfig:
 
 
 def llama_tiny(vocab: int = 512) -> LlamaConfig:
-    """Tiny config for tests. head_dim stays 128 (HIP kernel contract)."""
+    """Tiny config for tests at head_dim 128."""
     return LlamaConfig(name="llama-tiny", vocab_size=vocab, hidden_size=256,
                        n_layers=2, n_heads=2, n_kv_heads=1, ffn_dim=512,
                        max_seq_len=512)
+
+
+def llama_tiny_d64(vocab: int = 512) -> LlamaConfig:
+    """Tiny head-dim-64 config for the serving tests (4 q-heads on 1
+    kv-head). As in llama3_2_1b, embeddings are not tied and rope is not
+    scaled."""
+    return LlamaConfig(name="llama-tiny-d64", vocab_size=vocab,
+                       hidden_size=256, n_layers=2, n_heads=4, n_kv_heads=1,
+                       head_dim=64, ffn_dim=512, max_seq_len=512)
 
 
 def llama_moe_tiny(vocab: int = 512) -> LlamaConfig:

@@ -522,7 +522,7 @@ def decode_rope_store(qkv: torch.Tensor, cache_k: torch.Tensor,
     D = cache_k.shape[3]
     n = qkv.shape[0]
     q = torch.empty(n, n_heads, D, dtype=qkv.dtype, device=qkv.device)
-    if (_use_native(qkv) and qkv.dtype == torch.bfloat16 and D == 128):
+    if (_use_native(qkv) and qkv.dtype == torch.bfloat16 and D in (64, 128)):
         lib = _backend.require()
         _index_arg("decode_rope_store", "slots", slots, torch.int32, n, qkv)
         _index_arg("decode_rope_store", "positions", positions, torch.int64,
@@ -1175,6 +1175,52 @@ def layer_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
 
 # --------------------------------------------------------- Decode attention --
 
+def _attn64_cache(op: str, q: torch.Tensor, kcache, vcache, slots, starts,
+                  lens, max_rows: int, scale: float):
+    """kf_attn64_cache (attention_cache64.hip): the D = 64 kernel behind
+    attention_decode, attention_verify and attention_prefill. q [R,Hq,64]
+    bf16 contiguous; starts None gives sequence n the rows
+    [n*max_rows, (n+1)*max_rows).
+
+    Key splits come from (N, Hkv, max_rows) only, so a captured call has a
+    fixed shape: 1 when the grid already has two blocks for each of the 256
+    CUs, else enough to get there, at most 8. KF_DECODE_SPLITS overrides."""
+    lib = _backend.require()
+    R, Hq, D = q.shape
+    N = slots.shape[0] if isinstance(slots, torch.Tensor) else 0
+    Hkv = kcache.shape[2]
+    rows = max(1, min(int(max_rows), R)) * (Hq // Hkv)
+    tile = 32 if rows <= 32 else 64 if rows <= 64 else 128
+    blocks = max(1, N * Hkv * ((rows + tile - 1) // tile))
+    splits = int(os.environ.get("KF_DECODE_SPLITS", "0")) or \
+        min(8, max(1, 512 // blocks))
+    _index_arg(op, "slots", slots, torch.int32, N, q)
+    if starts is not None:
+        _index_arg(op, "starts", starts, torch.int32, N + 1, q)
+    _index_arg(op, "lens", lens, torch.int32, N, q)
+    out = torch.empty_like(q)
+    po = pm = None
+    if splits > 1:
+        po = torch.empty(R * Hq, splits, D, dtype=torch.float32,
+                         device=q.device)
+        pm = torch.empty(R * Hq, splits, 2, dtype=torch.float32,
+                         device=q.device)
+    _backend.check(
+        lib.kf_attn64_cache(_p(out), _p(po), _p(pm), _p(q), _p(kcache),
+                            _p(vcache), _i32p(slots), _i32p(starts),
+                            _i32p(lens), N, R, int(max_rows),
+                            kcache.shape[1], kcache.shape[0], Hq, Hkv, D,
+                            splits, float(scale),
+                            _stream()),
+        "attn64_cache")
+    return out
+
+
+def _attn64_cache_ok(q: torch.Tensor, Hq: int, Hkv: int, D: int) -> bool:
+    return (D == 64 and q.dtype == torch.bfloat16 and Hkv > 0
+            and Hq % Hkv == 0 and Hq // Hkv in (1, 2, 4, 8))
+
+
 def attention_decode(q: torch.Tensor, kcache: torch.Tensor,
                      vcache: torch.Tensor, slots: torch.Tensor,
                      lens: torch.Tensor, scale: Optional[float] = None):
@@ -1182,12 +1228,16 @@ def attention_decode(q: torch.Tensor, kcache: torch.Tensor,
 
     q [N,Hq,D] bf16; kcache/vcache [SLOTS,SMAX,Hkv,D] bf16;
     slots/lens int32 [N] (checked on the native path: the kernel reads them
-    at that width). Returns o [N,Hq,D].
+    at that width). Returns o [N,Hq,D]. D = 128 runs kf_attn_decode; D = 64
+    runs kf_attn64_cache with one row per sequence.
     """
     N, Hq, D = q.shape
     Hkv = kcache.shape[2]
     if scale is None:
         scale = D ** -0.5
+    if _use_native(q) and _attn64_cache_ok(q, Hq, Hkv, D):
+        return _attn64_cache("attention_decode", q.contiguous(), kcache,
+                             vcache, slots, None, lens, 1, scale)
     if _use_native(q):
         lib = _backend.require()
         _index_arg("attention_decode", "slots", slots, torch.int32, N, q)
@@ -1241,14 +1291,20 @@ def attention_verify(q: torch.Tensor, kcache: torch.Tensor,
     q [N,T,Hq,D] bf16, T new tokens per sequence whose K/V rows are already
     in the cache; kcache/vcache [SLOTS,SMAX,Hkv,D] bf16; slots/lens int32 [N].
     lens[n] is the number of keys token 0 sees (what attention_decode takes
-    for it); token t sees t more. Returns o [N,T,Hq,D]. The native kernel
-    (kf_attn_verify) takes T <= 8 and (Hq/Hkv)*T <= 32; anything else, the
-    CPU and fp32 go row by row through attention_decode's reference path.
+    for it); token t sees t more. Returns o [N,T,Hq,D]. The D = 128 kernel
+    (kf_attn_verify) takes T <= 8 and (Hq/Hkv)*T <= 32; the D = 64 kernel
+    (kf_attn64_cache, T rows per sequence) takes any T >= 1. Anything else,
+    the CPU and fp32 go row by row through attention_decode's reference path.
     """
     N, T, Hq, D = q.shape
     Hkv = kcache.shape[2]
     if scale is None:
         scale = D ** -0.5
+    if _use_native(q) and T >= 1 and _attn64_cache_ok(q, Hq, Hkv, D):
+        o = _attn64_cache("attention_verify",
+                          q.contiguous().view(N * T, Hq, D), kcache, vcache,
+                          slots, None, lens, T, scale)
+        return o.view(N, T, Hq, D)
     if (_use_native(q) and q.dtype == torch.bfloat16 and 1 <= T <= 8
             and (Hq // Hkv) * T <= 32):
         lib = _backend.require()
@@ -1293,15 +1349,23 @@ def attention_prefill(q: torch.Tensor, kcache: torch.Tensor,
     [N+1]. max_rows is a host bound on any sequence's row count (it sizes the
     grid; rows past it are not computed). Returns o [R,Hq,D]; rows outside
     every range are left unwritten. The three index tensors are read on the
-    device only, so a captured call follows their contents. The CPU, fp32 and
-    D != 128 expand the rows on the host and go through attention_decode's
-    reference path.
+    device only, so a captured call follows their contents. D = 128 runs
+    kf_attn_prefill; D = 64 runs kf_attn64_cache, which also splits the key
+    range over blocks when (N, Hkv, max_rows) alone would underfill the chip.
+    The CPU, fp32 and other head dims expand the rows on the host and go
+    through attention_decode's reference path.
     """
     R, Hq, D = q.shape
     N = slots.shape[0] if isinstance(slots, torch.Tensor) else 0
     Hkv = kcache.shape[2]
     if scale is None:
         scale = D ** -0.5
+    if _use_native(q) and _attn64_cache_ok(q, Hq, Hkv, D):
+        if not isinstance(starts, torch.Tensor):
+            raise TypeError("attention_prefill: starts must be a tensor, got "
+                            f"{type(starts).__name__}")
+        return _attn64_cache("attention_prefill", q.contiguous(), kcache,
+                             vcache, slots, starts, lens, max_rows, scale)
     if (_use_native(q) and q.dtype == torch.bfloat16 and D == 128
             and Hq // Hkv in (1, 2, 4, 8)):
         lib = _backend.require()

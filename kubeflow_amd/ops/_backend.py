@@ -146,6 +146,9 @@ SIGNATURES: dict[str, list] = {
     # out, q, kcache, vcache, slots, starts, lens, N, R, max_rows, smax,
     # n_slots, Hq, Hkv, D, scale, stream
     "kf_attn_prefill": [_P] * 4 + [_PI32] * 3 + [_I64] * 8 + [_F, _P],
+    # out, part_o, part_ml, q, kcache, vcache, slots, starts, lens, N, R,
+    # max_rows, smax, n_slots, Hq, Hkv, D, splits, scale, stream
+    "kf_attn64_cache": [_P] * 6 + [_PI32] * 3 + [_I64] * 9 + [_F, _P],
     # mixture of experts (moe.hip): ..., T, E | k | h ..., stream
     "kf_moe_route": [_P, _FP, _P, _P, _I64, _I64, _I64, _P],
     "kf_moe_route_bwd": [_P, _P, _FP, _P, _I64, _I64, _I64, _P],

@@ -43,6 +43,7 @@ EXTRA_CFLAGS = {
     "sample.hip": _NO_PK_F32,
     "attention_verify.hip": _NO_PK_F32,
     "attention_prefill.hip": _NO_PK_F32,
+    "attention_cache64.hip": _NO_PK_F32,
 }
 
 

@@ -11,7 +11,8 @@
 // into cache row [slot, pos]. One launch, no intermediate copies.
 //
 // Grid (N, Hq + 2*Hkv): one 64-lane wave per (sequence, head); lane d
-// owns the rotate-half pair (x[d], x[d + D/2]). D == 128.
+// owns the rotate-half pair (x[d], x[d + D/2]). D == 128; D == 64 has a
+// kernel of its own below (two heads per wave).
 
 #include "kf_common.h"
 
@@ -57,12 +58,57 @@ __global__ __launch_bounds__(64) void kf_decode_rope_store_kernel(
   }
 }
 
+// D == 64: a head is 32 rotate-half pairs, so one 64-lane wave takes two
+// heads. Grid (N, ceil((Hq + 2*Hkv) / 2)); lanes 0-31 own head 2y, lanes
+// 32-63 head 2y + 1, each lane the pair (x[d], x[d + 32]). The arithmetic is
+// the D == 128 kernel's, for the reason given there.
+__global__ __launch_bounds__(64) void kf_decode_rope_store64_kernel(
+    unsigned short* __restrict__ qout, unsigned short* __restrict__ ck,
+    unsigned short* __restrict__ cv, const unsigned short* __restrict__ qkv,
+    const float* __restrict__ cost, const float* __restrict__ sint,
+    const int* __restrict__ slots, const long long* __restrict__ positions,
+    int Hq, int Hkv, int64_t smax) {
+  const int D = 64, halfD = 32;
+  const int n = blockIdx.x;
+  const int h = blockIdx.y * 2 + (threadIdx.x >> 5);
+  const int d = threadIdx.x & 31;
+  const int Ht = Hq + 2 * Hkv;
+  if (h >= Ht) return;  // odd head count: the last wave's upper half
+  const long long pos = positions[n];
+  const unsigned short* src = qkv + ((int64_t)n * Ht + h) * D;
+  const int64_t crow = ((int64_t)slots[n] * smax + pos) * Hkv;
+
+  if (h < Hq + Hkv) {  // q or k head: rotate
+    const float c = cost[pos * halfD + d];
+    const float s = sint[pos * halfD + d];
+    const float a = kf_bf16_to_f32(src[d]);
+    const float b = kf_bf16_to_f32(src[d + halfD]);
+    unsigned short* dst = h < Hq ? qout + ((int64_t)n * Hq + h) * D
+                                 : ck + (crow + (h - Hq)) * D;
+    dst[d] = kf_f32_to_bf16(__builtin_fmaf(a, c, -(b * s)));
+    dst[d + halfD] = kf_f32_to_bf16(__builtin_fmaf(b, c, a * s));
+  } else {  // v head: plain copy into the cache
+    unsigned short* dst = cv + (crow + (h - Hq - Hkv)) * D;
+    dst[d] = src[d];
+    dst[d + halfD] = src[d + halfD];
+  }
+}
+
 KF_EXPORT int kf_decode_rope_store(void* qout, void* ck, void* cv,
                                    const void* qkv, const float* cost,
                                    const float* sint, const int* slots,
                                    const void* positions, int64_t N,
                                    int64_t Hq, int64_t Hkv, int64_t D,
                                    int64_t smax, void* stream) {
+  if (D == 64) {
+    dim3 grid64((unsigned)N, (unsigned)((Hq + 2 * Hkv + 1) / 2));
+    hipLaunchKernelGGL(kf_decode_rope_store64_kernel, grid64, dim3(64), 0,
+                       (hipStream_t)stream, (unsigned short*)qout,
+                       (unsigned short*)ck, (unsigned short*)cv,
+                       (const unsigned short*)qkv, cost, sint, slots,
+                       (const long long*)positions, (int)Hq, (int)Hkv, smax);
+    return (int)hipGetLastError();
+  }
   if (D != DF_D) return (int)hipErrorInvalidValue;
   dim3 grid((unsigned)N, (unsigned)(Hq + 2 * Hkv));
   hipLaunchKernelGGL(kf_decode_rope_store_kernel, grid, dim3(64), 0,

@@ -235,3 +235,13 @@ KF_EXPORT int kf_attn_prefill(void* out, const void* q, const void* kcache,
     const void* vcache, const int* slots, const int* starts, const int* lens,
     int64_t N, int64_t R, int64_t max_rows, int64_t smax, int64_t n_slots,
     int64_t Hq, int64_t Hkv, int64_t D, float scale, void* stream);
+
+// ---- D = 64 decode / verify / ragged prefill attention over the KV cache
+// (attention_cache64.hip). kf_attn_prefill's contract at q/out [R, Hq, 64];
+// starts == null: sequence n owns rows [n*max_rows, (n+1)*max_rows);
+// splits > 1 needs part_o [R*Hq, splits, 64] and part_ml [R*Hq, splits, 2] f32
+KF_EXPORT int kf_attn64_cache(void* out, void* part_o, void* part_ml,
+    const void* q, const void* kcache, const void* vcache, const int* slots,
+    const int* starts, const int* lens, int64_t N, int64_t R,
+    int64_t max_rows, int64_t smax, int64_t n_slots, int64_t Hq, int64_t Hkv,
+    int64_t D, int64_t splits, float scale, void* stream);

@@ -691,7 +691,11 @@ class InferenceEngine:
         [pos, pos+C) fill and the chunk attends the whole prefix via the
         rectangular-causal kernel — or, with prefill_ragged, as a one-
         sequence ragged forward: no 256-row pad and no slab view."""
-        if self.prefill_ragged:
+        # head_dim 64 has no rectangular kernel: chunks and prefix-cache
+        # tails always go ragged (ops.attention_prefill -> kf_attn64_cache).
+        # Whole equal-length prompts keep _prefill_many: flash_attention's
+        # D = 64 causal kernel takes any length.
+        if self.prefill_ragged or self.model.cfg.head_dim == 64:
             return self._ragged_hidden([chunk], [req.slot], [pos])[0]
         cfg = self.model.cfg
         C = len(chunk)
