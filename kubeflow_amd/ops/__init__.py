@@ -32,7 +32,7 @@ __all__ = [
     "skinny_linear", "kv_store",
     "decode_rope_store", "skinny_linear_q8", "quantize_fp8_rows",
     "dequantize_fp8_rows", "skinny_linear_q4", "quantize_mxfp4_rows",
-    "dequantize_mxfp4_rows",
+    "dequantize_mxfp4_rows", "linear_q4",
     "cross_entropy", "fused_adamw", "rope_cos_sin", "native_available",
     "masked_attention",
     "swiglu", "fused_qkv_attention",
@@ -506,6 +506,51 @@ def skinny_linear_q4(x: torch.Tensor, w4: torch.Tensor, scale: torch.Tensor,
     kernel rejects: F.linear on the dequantized weights."""
     _check_mxfp4("skinny_linear_q4", x, w4, scale)
     return _skinny(x, w4, scale, residual)
+
+
+def _gemm_q4_shape_ok(rows: int, N: int, K: int) -> bool:
+    """The shape rule of gemm_q4.hip (kf_gemm_q4)."""
+    return rows >= 1 and K >= 128 and K % 128 == 0 and N >= 32 and N % 32 == 0
+
+
+def linear_q4(x: torch.Tensor, w4: torch.Tensor, scale: torch.Tensor,
+              residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """MXFP4 linear y = x @ dequant(w4, scale)^T (+ residual) for any number
+    of rows, on the pair quantize_mxfp4_rows returns. Up to 32 rows on a shape
+    the skinny kernel takes it is skinny_linear_q4, bit for bit; above that
+    kf_gemm_q4 (gemm_q4.hip), the 128 x 128 tile GEMM that keeps W packed in
+    LDS and converts fragments in registers (K % 128 == 0, N % 32 == 0):
+    the prefill linears of an engine that holds no bf16 copy of its weights
+    (quant_prefill). Off the GPU and for shapes neither kernel takes:
+    F.linear on the dequantized weights. Inference only (no autograd)."""
+    _check_mxfp4("linear_q4", x, w4, scale)
+    shape = x.shape
+    M = 1
+    for d in shape[:-1]:
+        M *= int(d)
+    K = shape[-1]
+    N = w4.shape[0]
+    if M <= 32 and _skinny_shape_ok(M, N, K, "q4"):
+        return _skinny(x, w4, scale, residual)
+    if (not _use_native(x) or x.dtype != torch.bfloat16
+            or not _gemm_q4_shape_ok(M, N, K)):
+        y = torch.nn.functional.linear(
+            x, dequantize_mxfp4_rows(w4, scale, x.dtype))
+        return y + residual if residual is not None else y
+    lib = _backend.require()
+    x2 = x.reshape(M, K)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    r2 = None
+    if residual is not None:
+        r2 = residual.reshape(M, N)
+        if not r2.is_contiguous():
+            r2 = r2.contiguous()
+    y = torch.empty(M, N, dtype=x.dtype, device=x.device)
+    _backend.check(
+        lib.kf_gemm_q4(_p(y), _p(x2), _p(w4), _p(scale), _p(r2), M, N, K,
+                       0, 0, 0, _stream()), "gemm_q4")
+    return y.view(*shape[:-1], N)
 
 
 def decode_rope_store(qkv: torch.Tensor, cache_k: torch.Tensor,

@@ -106,6 +106,7 @@ SIGNATURES: dict[str, list] = {
     "kf_skinny_gemm": [_P, _P, _P, _P] + [_I64] * 6 + [_P],
     "kf_skinny_gemm_q8": [_P, _P, _P, _FP, _P] + [_I64] * 6 + [_P],
     "kf_skinny_gemm_q4": [_P, _P, _P, _P, _P] + [_I64] * 6 + [_P],
+    "kf_gemm_q4": [_P, _P, _P, _P, _P] + [_I64] * 6 + [_P],
     # c, a, w_bank | w8, wscale, offsets, a_rows, n_groups, max_rows,
     # total_rows, a_nrows, N, K, stream
     "kf_skinny_gemm_grouped": [_P, _P, _P, _PI32, _PI32] + [_I64] * 6 + [_P],

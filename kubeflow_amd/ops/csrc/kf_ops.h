@@ -78,6 +78,11 @@ KF_EXPORT int kf_skinny_gemm_q8(void* c, const void* a, const void* w8,
 KF_EXPORT int kf_skinny_gemm_q4(void* c, const void* a, const void* w4,
     const unsigned char* wscale, const void* res, int64_t M, int64_t N,
     int64_t K, int64_t lda, int64_t ldw, int64_t ldc, void* stream);
+// gemm_q4.hip: the same product for any M >= 1 (128 x 128 tile GEMM); K % 128
+// == 0, N % 32 == 0
+KF_EXPORT int kf_gemm_q4(void* c, const void* a, const void* w4,
+    const unsigned char* wscale, const void* res, int64_t M, int64_t N,
+    int64_t K, int64_t lda, int64_t ldw, int64_t ldc, void* stream);
 // grouped over device offsets (routed MoE decode): group e owns rows
 // [offsets[e], offsets[e+1]) of c and reads a through a_rows (nullable)
 KF_EXPORT int kf_skinny_gemm_grouped(void* c, const void* a,

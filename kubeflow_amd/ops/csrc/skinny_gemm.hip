@@ -23,6 +23,7 @@
 // Grid = N/16 blocks (x n_groups); bf16 in/out, fp32 accumulate.
 
 #include "kf_common.h"
+#include "kf_fp4.h"
 
 typedef __bf16 kf_bf16x8s __attribute__((ext_vector_type(8)));
 typedef float kf_f32x4s __attribute__((ext_vector_type(4)));
@@ -420,22 +421,7 @@ __device__ __forceinline__ void kf_sk_q8_body(
 #define SK4_ROWB (SK4_KC / 2)       // ... = 512 B per row
 #define SK4_STRIDE (SK4_ROWB + 16)  // row slice bytes + pad (132 words)
 
-typedef __bf16 kf_bf16x2s __attribute__((ext_vector_type(2)));
-
-// 8 e2m1 values of one word (element j in nibble j) times 2^(sbyte - 127)
-__device__ __forceinline__ kf_bf16x8s kf_fp4x8_to_bf16x8(unsigned int w,
-                                                         unsigned int sbyte) {
-  const float sc = __builtin_bit_cast(float, sbyte << 23);
-  union {
-    kf_bf16x2s p[4];
-    kf_bf16x8s v;
-  } out;
-  out.p[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 0);
-  out.p[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 1);
-  out.p[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 2);
-  out.p[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 3);
-  return out.v;
-}
+// kf_fp4x8_to_bf16x8 (kf_fp4.h): 8 e2m1 values of one word times the scale
 
 // p.ldw counts fp4 elements: W rows are ldw / 2 bytes, scale rows ldw / 32
 template <int MT>

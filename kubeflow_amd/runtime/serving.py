@@ -145,6 +145,28 @@ def moe_decode_mode() -> str:
 QUANT_FORMATS = ("fp8", "mxfp4")
 
 
+def skinny_selection() -> set:
+    """KF_SKINNY: the decode linears that go through the weight-streaming
+    kernels (and, under KF_SERVE_QUANT, read the quantized weights): "small"
+    (the default), "all" (adds lm_head), "off", or a comma-separated list of
+    qkv, wo, w13, w2, lm."""
+    mode = os.environ.get("KF_SKINNY", "small")
+    return {"small": {"qkv", "wo", "w13", "w2"}, "off": set(),
+            "all": {"qkv", "wo", "w13", "w2", "lm"}}.get(
+                mode, set(mode.split(",")))
+
+
+def _tensors(obj) -> list:
+    """The tensors of a nest of lists, tuples and dicts (None: none)."""
+    if isinstance(obj, torch.Tensor):
+        return [obj]
+    if isinstance(obj, dict):
+        obj = list(obj.values())
+    if isinstance(obj, (list, tuple)):
+        return [t for o in obj for t in _tensors(o)]
+    return []
+
+
 def quantize_moe_banks(moe, fmt: str = "fp8"):
     """((w13_8, w13_scale), (w2_8, w2_scale)): the two expert banks of an
     MoEMLP through ops.quantize_fp8_rows on their flattened [E * out, in]
@@ -162,7 +184,8 @@ class InferenceEngine:
     def __init__(self, model_name: str, device=None, max_slots: int = 32,
                  smax: int = 4096, max_batch: int = 32,
                  storage_uri: str | None = None,
-                 quant: str | None = None):
+                 quant: str | None = None,
+                 quant_prefill: bool | None = None):
         self.device = device or (torch.device("cuda", 0)
                                  if torch.cuda.is_available()
                                  else torch.device("cpu"))
@@ -192,6 +215,7 @@ class InferenceEngine:
             self.cache = None
             self.quant = False
             self.quant_format = None
+            self.quant_prefill = False
             self._qw = None
             self.use_graphs = False
             self._graphs = {}
@@ -211,7 +235,8 @@ class InferenceEngine:
             return
         # KF_SERVE_QUANT=fp8: per-output-row OCP e4m3 weight-only quant
         # for the DECODE linears (W8A16 — halves the weight traffic the
-        # decode step is bound by; prefill keeps the bf16 weights).
+        # decode step is bound by; prefill keeps the bf16 weights, unless
+        # quant_prefill below moves it onto the MXFP4 ones and drops them).
         # Applied after storageUri load so trained weights quantize.
         if quant is None:
             quant = os.environ.get("KF_SERVE_QUANT", "off")
@@ -224,6 +249,24 @@ class InferenceEngine:
         self.quant_format = quant if self.quant else None
         self._qw = None
         moe = bool(getattr(cfg, "n_experts", 0))
+        # KF_SERVE_QUANT_PREFILL=1 (with mxfp4): prefill runs wqkv, wo, w13
+        # and w2 through ops.linear_q4 (kf_gemm_q4) on the same MXFP4 pairs
+        # as decode, and the bf16 storage of those weights is released: the
+        # model is served from the 4-bit copy alone. Off by default.
+        if quant_prefill is None:
+            quant_prefill = os.environ.get("KF_SERVE_QUANT_PREFILL",
+                                           "0") != "0"
+        self.quant_prefill = bool(quant_prefill)
+        if self.quant_prefill:
+            missing = {"qkv", "wo", "w13", "w2"} - skinny_selection()
+            why = (f"it needs quant='mxfp4', got {quant!r}"
+                   if quant != "mxfp4" else
+                   f"{cfg.name} is an MoE model, whose experts prefill "
+                   "through their bf16 banks" if moe else
+                   f"KF_SKINNY leaves {sorted(missing)} of the decode step on "
+                   "the bf16 weights it would release" if missing else None)
+            if why:
+                raise ValueError(f"quant_prefill: {why}")
         if self.quant and moe and not self._moe_quant_usable(max_batch):
             # the dense MoE decode has no quantized experts: as before, such
             # a model serves bf16 weights throughout
@@ -248,6 +291,20 @@ class InferenceEngine:
             # lm_head stays bf16 under "small" routing (sampling
             # sensitivity); KF_SKINNY=all opts it into the format too
             self._q_lm = quantize(self.model.lm_head.weight)
+        if self.quant_prefill:
+            # nothing reads these four any more: _decode_forward takes the
+            # pairs (the KF_SKINNY check above) and prefill _prefill_linear
+            for layer in self.model.layers:
+                for n in ("wqkv", "wo", "w13", "w2"):
+                    w = getattr(layer, n).weight
+                    getattr(layer, n).weight = torch.nn.Parameter(
+                        w.new_empty(0), requires_grad=False)
+        # resident weight bytes: the model's parameters and the quantized
+        # copies next to them
+        self.weight_bytes = sum(
+            t.numel() * t.element_size()
+            for t in list(self.model.parameters()) + _tensors(
+                [self._qw, getattr(self, "_q_lm", None)]))
         smax = min(smax, cfg.max_seq_len)
         self.cache = KVCache(cfg.n_layers, max_slots, smax,
                              cfg.n_kv_heads, cfg.head_dim, self.device, dtype)
@@ -699,12 +756,11 @@ class InferenceEngine:
             return self._ragged_hidden([chunk], [req.slot], [pos])[0]
         cfg = self.model.cfg
         C = len(chunk)
-        import torch.nn.functional as F
         tokens = torch.tensor([chunk], dtype=torch.int64, device=self.device)
         x = self.model.embed(tokens)
         cos, sin = self.model.rope_cos, self.model.rope_sin
         for li, layer in enumerate(self.model.layers):
-            qkv = F.linear(layer.attn_norm(x), layer.wqkv.weight)
+            qkv = self._prefill_linear(li, layer, "wqkv", layer.attn_norm(x))
             q, k, v = qkv.split([cfg.n_heads * cfg.head_dim,
                                  cfg.n_kv_heads * cfg.head_dim,
                                  cfg.n_kv_heads * cfg.head_dim], dim=-1)
@@ -718,14 +774,10 @@ class InferenceEngine:
             kv_v = self.cache.v[li][req.slot:req.slot + 1, :pos + C]
             o = ops.flash_attention_rect(q, kv_k, kv_v, q_offset=pos,
                                          scale=cfg.head_dim ** -0.5)
-            o = layer.wo(o.reshape(1, C, cfg.n_heads * cfg.head_dim))
-            x = x + o
-            if layer.moe is not None:
-                x = x + layer.moe(layer.mlp_norm(x))
-            else:
-                g, u = F.linear(layer.mlp_norm(x), layer.w13.weight).split(
-                    [cfg.ffn_dim, cfg.ffn_dim], dim=-1)
-                x = x + layer.w2(F.silu(g) * u)
+            x = self._prefill_linear(
+                li, layer, "wo",
+                o.reshape(1, C, cfg.n_heads * cfg.head_dim), residual=x)
+            x = self._prefill_mlp(li, layer, x)
         return x
 
     @torch.no_grad()
@@ -739,7 +791,6 @@ class InferenceEngine:
         ops.attention_prefill reads K/V in place. Returns the hidden rows
         [1, R, h] and each chunk's last row index."""
         cfg = self.model.cfg
-        import torch.nn.functional as F
         counts = [len(c) for c in chunks]
         R = sum(counts)
         starts = [0]
@@ -762,20 +813,17 @@ class InferenceEngine:
         x = self.model.embed(tokens)
         cos, sin = self.model.rope_cos, self.model.rope_sin
         for li, layer in enumerate(self.model.layers):
-            qkv = F.linear(layer.attn_norm(x), layer.wqkv.weight)
+            qkv = self._prefill_linear(li, layer, "wqkv", layer.attn_norm(x))
             q = ops.decode_rope_store(qkv[0], self.cache.k[li],
                                       self.cache.v[li], cos, sin, row_slots,
                                       positions, cfg.n_heads, cfg.n_kv_heads)
             o = ops.attention_prefill(q, self.cache.k[li], self.cache.v[li],
                                       seq_slots, starts_t, lens, max(counts),
                                       scale=cfg.head_dim ** -0.5)
-            x = x + layer.wo(o.reshape(1, R, cfg.n_heads * cfg.head_dim))
-            if layer.moe is not None:
-                x = x + layer.moe(layer.mlp_norm(x))
-            else:
-                g, u = F.linear(layer.mlp_norm(x), layer.w13.weight).split(
-                    [cfg.ffn_dim, cfg.ffn_dim], dim=-1)
-                x = x + layer.w2(F.silu(g) * u)
+            x = self._prefill_linear(
+                li, layer, "wo",
+                o.reshape(1, R, cfg.n_heads * cfg.head_dim), residual=x)
+            x = self._prefill_mlp(li, layer, x)
         return x, [s - 1 for s in starts[1:]]
 
     @torch.no_grad()
@@ -836,8 +884,7 @@ class InferenceEngine:
     def _layer_prefill(self, layer, li, x, cos, sin, slots, S):
         cfg = self.model.cfg
         B = len(slots)
-        import torch.nn.functional as F
-        qkv = F.linear(layer.attn_norm(x), layer.wqkv.weight)
+        qkv = self._prefill_linear(li, layer, "wqkv", layer.attn_norm(x))
         q, k, v = qkv.split([cfg.n_heads * cfg.head_dim,
                              cfg.n_kv_heads * cfg.head_dim,
                              cfg.n_kv_heads * cfg.head_dim], dim=-1)
@@ -849,14 +896,30 @@ class InferenceEngine:
             self.cache.k[li][slot, :S] = k[gi]
             self.cache.v[li][slot, :S] = v[gi]
         o = ops.flash_attention(q, k, v, causal=True)
-        o = layer.wo(o.reshape(B, S, cfg.n_heads * cfg.head_dim))
-        x = x + o
+        x = self._prefill_linear(
+            li, layer, "wo", o.reshape(B, S, cfg.n_heads * cfg.head_dim),
+            residual=x)
+        return self._prefill_mlp(li, layer, x)
+
+    def _prefill_linear(self, li, layer, name, t, residual=None):
+        """One of layer li's four dense linears (wqkv, wo, w13, w2) in a
+        prefill path, (+ residual): F.linear on the bf16 weight, or, with
+        quant_prefill, ops.linear_q4 on the engine's MXFP4 pair, the residual
+        in the kernel's epilogue (the bf16 weight is released then)."""
+        if self.quant_prefill:
+            return ops.linear_q4(t, *self._qw[li][name], residual=residual)
+        y = torch.nn.functional.linear(t, getattr(layer, name).weight)
+        return y if residual is None else residual + y
+
+    def _prefill_mlp(self, li, layer, x):
+        """x + the layer's MLP block, shared by the three prefill paths."""
         if layer.moe is not None:  # MoE predictor (dense experts, EP=1)
             return x + layer.moe(layer.mlp_norm(x))
-        g, u = torch.nn.functional.linear(
-            layer.mlp_norm(x), layer.w13.weight).split(
-                [cfg.ffn_dim, cfg.ffn_dim], dim=-1)
-        return x + layer.w2(torch.nn.functional.silu(g) * u)
+        cfg = self.model.cfg
+        g, u = self._prefill_linear(li, layer, "w13", layer.mlp_norm(x)).split(
+            [cfg.ffn_dim, cfg.ffn_dim], dim=-1)
+        return self._prefill_linear(
+            li, layer, "w2", torch.nn.functional.silu(g) * u, residual=x)
 
     @torch.no_grad()
     def _decode_forward(self, tokens, positions, slots, lens, T=1,
@@ -875,10 +938,7 @@ class InferenceEngine:
         # profiles/r02_skinny_gemm.md), "all", or "off" (hipBLASLt
         # everywhere). The K14336 / N28672 / lm_head shapes stay on
         # hipBLASLt under "small": measured losses there.
-        mode = os.environ.get("KF_SKINNY", "small")
-        sel = {"small": {"qkv", "wo", "w13", "w2"}, "off": set(),
-               "all": {"qkv", "wo", "w13", "w2", "lm"}}.get(
-                   mode, set(mode.split(",")))
+        sel = skinny_selection()
         qw = self._qw if self.quant else None
         q4 = self.quant_format == "mxfp4"
         lin_q = ops.skinny_linear_q4 if q4 else ops.skinny_linear_q8
