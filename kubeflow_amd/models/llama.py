@@ -261,17 +261,50 @@ class MoEMLP(nn.Module):
         captured graph follows each replay's routing. q8: the two banks
         quantized per row, q4: in MXFP4 (see ops.moe_experts_decode). Where
         routed_decode_ok does not hold (the CPU, EP, more than 32 rows, bank
-        shapes the kernels reject) this is decode_dense on the bf16 banks."""
+        shapes the kernels reject) this is decode_dense on the bf16 banks,
+        except for q4 banks with more than 32 rows (a verify step) where
+        routed_q4_ok holds: those take prefill_routed."""
         if not self.routed_decode_ok(x, q8=q8 is not None,
                                      q4=q4 is not None):
+            T = x.numel() // max(1, x.shape[-1])
+            if q4 is not None and T > 32 and self.routed_q4_ok(x):
+                return self.prefill_routed(x, q4)
             return self.decode_dense(x)
         N, S, h = x.shape
         xf = x.reshape(N * S, h)
         logits = torch.nn.functional.linear(xf, self.gate.weight)
-        out = ops.moe_experts_decode(xf, logits, self.experts_w13,
-                                     self.experts_w2, self.cfg.top_k, q8=q8,
-                                     q4=q4)
+        if q4 is not None:   # the same call; E from the logits, not the banks
+            out = ops.moe_experts_q4(xf, logits, q4, self.cfg.top_k)
+        else:
+            out = ops.moe_experts_decode(xf, logits, self.experts_w13,
+                                         self.experts_w2, self.cfg.top_k,
+                                         q8=q8)
         return out.view(N, S, h)
+
+    def routed_q4_ok(self, x) -> bool:
+        """True if prefill_routed(x, q4) runs kf_gemm_q4_grouped: EP = 1, the
+        moe.hip path usable for x's rows (bf16 on the GPU) and both banks
+        within that kernel's shapes, whatever the row count."""
+        cfg = self.cfg
+        h, f = cfg.hidden_size, cfg.ffn_dim
+        return (self.ep is None
+                and ops.moe_native_ok(x.reshape(-1, x.shape[-1]),
+                                      cfg.n_experts, cfg.top_k)
+                and self.gate.weight.dtype == x.dtype
+                and ops.grouped_gemm_q4_ok(2 * f, h, x.dtype, swiglu=True)
+                and ops.grouped_gemm_q4_ok(h, f, x.dtype))
+
+    @torch.no_grad()
+    def prefill_routed(self, x, q4):
+        """The routed block on the MXFP4 banks alone (q4 as
+        quantize_moe_banks(fmt="mxfp4") returns them), for any number of rows
+        and without a host sync: ops.moe_experts_q4. It reads neither
+        experts_w13 nor experts_w2, so an engine that holds q4 can release
+        them. The caller checks routed_q4_ok."""
+        h = x.shape[-1]
+        xf = x.reshape(-1, h)
+        logits = torch.nn.functional.linear(xf, self.gate.weight)
+        return ops.moe_experts_q4(xf, logits, q4, self.cfg.top_k).view(x.shape)
 
 
 class LlamaBlock(nn.Module):

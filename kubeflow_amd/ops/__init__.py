@@ -2118,6 +2118,127 @@ def grouped_skinny_linear_q4(x: torch.Tensor, w4: torch.Tensor,
                            w4.shape[0] // n, w4.shape[1] * 2)
 
 
+_swiglu = swiglu    # grouped_linear_q4 has a keyword of that name
+
+
+def grouped_gemm_q4_ok(N: int, K: int, dtype, swiglu: bool = False) -> bool:
+    """True if kf_gemm_q4_grouped takes [., N, K] MXFP4 banks (swiglu: N = 2f
+    with f % 32 == 0), whatever the row count: what a caller asks before it
+    captures a graph or releases the bf16 banks, since the fallback of
+    grouped_linear_q4 syncs and dequantizes."""
+    return (dtype == torch.bfloat16 and K >= 128 and K % 128 == 0
+            and N >= 32 and N % (64 if swiglu else 32) == 0)
+
+
+@torch.no_grad()
+def grouped_linear_q4(x: torch.Tensor, w4: torch.Tensor, scale: torch.Tensor,
+                      offsets: torch.Tensor,
+                      rows: Optional[torch.Tensor] = None, *,
+                      swiglu: bool = False,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """grouped_skinny_linear_q4 without its 32-row limit: the per-expert
+    linear over device offsets on an MXFP4 bank (w4 uint8 [n * N, K/2], scale
+    uint8 [n * N, K/32], n = offsets.numel() - 1 <= 64) for any number of
+    rows per expert, y[lo_e + i] = x[rows[lo_e + i] if rows is given else
+    lo_e + i] @ dq(bank[e]).T. swiglu=True: the bank is w13 (N = 2f, gate rows
+    then up rows) and y is silu(gate) * up, [R, f], from the fp32
+    accumulators with one rounding.
+
+    One launch of kf_gemm_q4_grouped (gemm_q4.hip): 128-row tiles found on the
+    device from `offsets`, no host sync, so it captures into a graph and a
+    replay follows the offsets of the day; rows at or past offsets[n] are not
+    written. With swiglu=False each expert's rows are, bit for bit,
+    kf_gemm_q4's for the same rows and bank slice.
+
+    Inference only. Off the GPU and for shapes grouped_gemm_q4_ok rejects:
+    reference.grouped_linear_offsets on the dequantized bank (then swiglu),
+    which reads offsets on the host and is not for capture."""
+    n = offsets.numel() - 1
+    if (w4.dim() != 2 or n < 1 or w4.shape[0] % n or w4.dtype != torch.uint8
+            or scale.dtype != torch.uint8 or (w4.shape[1] * 2) % 32
+            or scale.shape != (w4.shape[0], w4.shape[1] // 16)
+            or not w4.is_contiguous() or not scale.is_contiguous()):
+        raise ValueError(
+            f"grouped_linear_q4: w4 {tuple(w4.shape)} {w4.dtype}, scale "
+            f"{tuple(scale.shape)} {scale.dtype} and {n} experts do not "
+            "agree")
+    N, K = w4.shape[0] // n, w4.shape[1] * 2
+    if (x.dim() != 2 or x.shape[1] != K or offsets.dim() != 1
+            or (rows is not None and rows.dim() != 1) or (swiglu and N % 2)):
+        raise ValueError(
+            f"grouped_linear_q4: x {tuple(x.shape)}, bank [{n}, {N}, {K}], "
+            f"offsets {tuple(offsets.shape)}, rows "
+            f"{None if rows is None else tuple(rows.shape)} and "
+            f"swiglu={swiglu} do not agree")
+    total = x.shape[0] if rows is None else rows.numel()
+    n_out = N // 2 if swiglu else N
+    if out is not None and (out.dim() != 2 or out.shape[0] < total
+                            or out.shape[1] != n_out or out.dtype != x.dtype
+                            or not out.is_contiguous()):
+        raise ValueError(f"grouped_linear_q4: out must be a contiguous [>= "
+                         f"{total}, {n_out}] {x.dtype} tensor, got "
+                         f"{tuple(out.shape)}")
+    native = (_use_native(x) and offsets.dtype == torch.int32
+              and (rows is None or rows.dtype == torch.int32)
+              and n <= MOE_MAX_EXPERTS
+              and grouped_gemm_q4_ok(N, K, x.dtype, swiglu))
+    if not native:
+        wb = dequantize_mxfp4_rows(w4, scale, x.dtype)
+        y = reference.grouped_linear_offsets(x, wb.reshape(n, N, K), offsets,
+                                             rows)
+        if swiglu:
+            y = _swiglu(y)
+        if out is None:
+            return y
+        out[:total].copy_(y)
+        return out
+    lib = _backend.require()
+    x = x.contiguous()
+    offsets = offsets.contiguous()
+    if rows is not None:
+        rows = rows.contiguous()
+    if out is None:
+        out = torch.empty(total, n_out, dtype=x.dtype, device=x.device)
+    _backend.check(
+        lib.kf_gemm_q4_grouped(
+            _p(out), _p(x), _p(w4), _p(scale), _i32p(offsets), _i32p(rows), n,
+            total, x.shape[0], N, K, int(bool(swiglu)), _stream()),
+        "gemm_q4_grouped")
+    return out
+
+
+@torch.no_grad()
+def moe_experts_q4(x: torch.Tensor, logits: torch.Tensor, q4,
+                   top_k: int) -> torch.Tensor:
+    """The routed expert block on MXFP4 banks alone, for any number of token
+    rows and without a host sync: x [T, h], logits [T, E], q4 = ((w13_4,
+    w13_scale), (w2_4, w2_scale)) as quantize_moe_banks(fmt="mxfp4") returns
+    them -> [T, h].
+
+    Up to 32 rows on shapes the grouped skinny kernels take this is
+    moe_experts_decode(q4=...), bit for bit. Above: moe_route(sync=False),
+    grouped_linear_q4 on the w13 bank reading x through routing.src with the
+    SwiGLU in its epilogue (no gather launch, no [M, 2f] buffer, no swiglu
+    launch), grouped_linear_q4 on the w2 bank, moe_combine. Every buffer is
+    sized from T, k and the bank shapes, so a captured graph replays any
+    routing. For capture the caller checks grouped_gemm_q4_ok for both banks
+    first. Inference only."""
+    (w13_4, s13), (w2_4, s2) = q4
+    T, E = logits.shape
+    f2, h = w13_4.shape[0] // E, w13_4.shape[1] * 2
+    if (T <= GROUPED_SKINNY_MAX_ROWS
+            and grouped_skinny_ok(T, f2, h, x.dtype, q4=True)
+            and grouped_skinny_ok(T, h, f2 // 2, x.dtype, q4=True)):
+        # the banks' bf16 originals are not read on the q4 path: only E is
+        return moe_experts_decode(x, logits, x.new_empty(E, 0, 0), None,
+                                  top_k, q4=q4)
+    routing = moe_route(logits, top_k, 0, E, sync=False)
+    a = grouped_linear_q4(x, w13_4, s13, routing.offsets, routing.src,
+                          swiglu=True)
+    return moe_combine(grouped_linear_q4(a, w2_4, s2, routing.offsets),
+                       routing)
+
+
 @torch.no_grad()
 def moe_experts_decode(x: torch.Tensor, logits: torch.Tensor,
                        w13: torch.Tensor, w2: torch.Tensor, top_k: int,

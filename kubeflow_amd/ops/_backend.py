@@ -114,6 +114,10 @@ SIGNATURES: dict[str, list] = {
                                  [_I64] * 6 + [_P],
     "kf_skinny_gemm_grouped_q4": [_P, _P, _P, _P, _PI32, _PI32] +
                                  [_I64] * 6 + [_P],
+    # c, a, w4, wscale, offsets, a_rows, n_experts, total_rows, a_nrows, N,
+    # K, swiglu, stream
+    "kf_gemm_q4_grouped": [_P, _P, _P, _P, _PI32, _PI32] + [_I64] * 5 +
+                          [_I32, _P],
     "kf_kv_store": [_P] * 6 + [_I64, _I64, _I64, _P],
     "kf_decode_rope_store": [_P, _P, _P, _P, _FP, _FP, _PI32, _P] +
                             [_I64] * 5 + [_P],

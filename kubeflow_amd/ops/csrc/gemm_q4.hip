@@ -45,8 +45,14 @@
 // that. A wave skips its 32-row / 32-column MFMA tiles past M / N; blocks with
 // all tiles live run the same loop without the guards.
 //
-// Resource usage (hipcc -Rpass-analysis=kernel-resource-usage, gfx950):
-//   168 VGPRs, scratch 0, LDS 40,960 B, 3 waves/SIMD
+// Resource usage (hipcc -Rpass-analysis=kernel-resource-usage, gfx950), every
+// kernel scratch 0, LDS 40,960 B, 3 waves/SIMD:
+//   kf_gemm_q4_kernel                      168 VGPRs
+//   kf_gemm_q4_grouped_kernel<rows, swiglu>
+//     <0, 0> 165   <0, 1> 163   <1, 0> 147   <1, 1> 147 VGPRs
+// The grouped form (kf_gemm_q4_grouped, at the end of the file) runs the same
+// block per expert over device offsets; the body takes what differs between
+// the two as a kf_gq_prob.
 
 #include "kf_attn_common.h"
 #include "kf_fp4.h"
@@ -68,14 +74,18 @@ struct kf_gq_stage {
   kf_short8 a[4];
   kf_u32x4g w;
 
+  // GATHER: row j is row arow[j] of the matrix ag points into (its column
+  // chunk already added); else row 32 * j below ag
+  template <bool GATHER>
   __device__ __forceinline__ void load(const unsigned short* ag, int64_t lda,
+                                       const int (&arow)[4],
                                        const bool (&aok)[4],
                                        const unsigned char* wg, int64_t k0) {
     const kf_short8 zero = kf_short8{0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       a[j] = aok[j] ? *reinterpret_cast<const kf_short8*>(
-                          ag + (int64_t)(32 * j) * lda + k0)
+                          ag + (int64_t)(GATHER ? arow[j] : 32 * j) * lda + k0)
                     : zero;
     w = *reinterpret_cast<const kf_u32x4g*>(wg + (k0 >> 1));
   }
@@ -140,33 +150,82 @@ __device__ __forceinline__ void kf_gq_compute(
   }
 }
 
+// What one block computes, as its body sees it (kf_sk_prob's role in
+// skinny_gemm.hip): the 128 x 128 tile (tm, tn) of C[M, N] = A W^T (+ res).
+// The plain kernel fills it from its arguments and blockIdx; the grouped one
+// with the rows and the bank slice of the expert its prologue found. The body
+// takes no "grouped" flag.
+struct kf_gq_prob {
+  unsigned short* c;
+  const unsigned short* a;
+  const unsigned char* w4;
+  const unsigned char* wscale;
+  const unsigned short* res;  // nullable
+  const int* a_rows;          // GATHER bodies only: entry of problem row 0
+  int a_nrows;
+  int64_t M, N, K, lda, ldw, ldc;
+  int64_t tm, tn;  // the block's tile: rows 128 tm .., columns 128 tn ..
+                   // (SWIGLU: 64 tn ..)
+};
+
 // One block. GUARD = false: every tile of the block is live (block-uniform,
 // chosen by the kernel below). The two instantiations are whole bodies, not a
 // branch per stage: with both MFMA sequences inside one K loop the register
 // allocator spilled (168 VGPRs + 336 B of scratch).
-template <bool GUARD>
-__device__ __forceinline__ void kf_gq_body(
+//
+// GATHER: A row m of the problem is row a_rows[m] of a, clamped into
+// [0, a_nrows). Only the stager changes: its four rows become four indices.
+// SWIGLU: W is a w13 bank slice [2 N, K], gate rows then up rows, and the
+// block makes 64 columns (n0 = 64 tn) of silu(gate) * up. Its 128
+// staged W rows are 64 gate rows and their 64 up rows, LDS row r holding
+//   W row (r>>5 & 1 ? N : 0) + n0 + 32 * (r>>6) + (r & 31),
+// so wave wn has gate in its n-tile j = 0 and up in j = 1 for the same 32
+// columns n0 + 32 wn .., in the same lane and register index; the epilogue
+// multiplies the fp32 accumulators and rounds once. The LDS layout and
+// kf_gq_compute do not know.
+//
+// kf_gq_body (below) unpacks a kf_gq_prob into these parameters: the
+// __restrict__ qualifiers have to sit on function parameters to reach the
+// inlined loads and stores.
+template <bool GUARD, bool GATHER, bool SWIGLU>
+__device__ __forceinline__ void kf_gq_tile(
     unsigned short* __restrict__ c, const unsigned short* __restrict__ a,
     const unsigned char* __restrict__ w4,
     const unsigned char* __restrict__ wscale,
     const unsigned short* __restrict__ res, int64_t M, int64_t N, int64_t K,
-    int64_t lda, int64_t ldw, int64_t ldc,
+    int64_t lda, int64_t ldw, int64_t ldc, int64_t tm, int64_t tn,
+    const int* __restrict__ a_rows, int a_nrows,
     unsigned char (&a_lds)[2][GQ_A_TILEB],
     unsigned char (&w_lds)[2][GQ_W_TILEB]) {
   const int tid = threadIdx.x;
   const int wv = tid / KF_WAVE, wm = wv >> 1, wn = wv & 1;
   const int lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
-  const int64_t m0 = (int64_t)blockIdx.x * GQ_BM;
-  const int64_t n0 = (int64_t)blockIdx.y * GQ_BN;
+  const int64_t m0 = tm * GQ_BM;
+  const int64_t n0 = tn * (SWIGLU ? GQ_BN / 2 : GQ_BN);
 
   // staging: this thread's 4 A rows (zeros past M) and its W row (a row past
   // N reads row N - 1: its tiles are never multiplied)
   bool aok[4];
+  int gidx[4] = {0, 0, 0, 0};
 #pragma unroll
-  for (int j = 0; j < 4; ++j) aok[j] = m0 + (tid >> 3) + 32 * j < M;
+  for (int j = 0; j < 4; ++j) {
+    aok[j] = m0 + (tid >> 3) + 32 * j < M;
+    if (GATHER && aok[j]) {
+      const int s = a_rows[m0 + (tid >> 3) + 32 * j];
+      gidx[j] = s < 0 ? 0 : (s >= a_nrows ? a_nrows - 1 : s);
+    }
+  }
   const unsigned short* ag =
-      a + (aok[0] ? m0 + (tid >> 3) : 0) * lda + (tid & 7) * 8;
-  const int64_t wrow = n0 + (tid >> 1) < N ? n0 + (tid >> 1) : N - 1;
+      GATHER ? a + (tid & 7) * 8
+             : a + (aok[0] ? m0 + (tid >> 3) : 0) * lda + (tid & 7) * 8;
+  int64_t wrow;
+  if (SWIGLU) {
+    const int r = tid >> 1;
+    const int64_t o = n0 + 32 * (r >> 6) + (r & 31);
+    wrow = (o < N ? o : N - 1) + ((r >> 5) & 1 ? N : 0);
+  } else {
+    wrow = n0 + (tid >> 1) < N ? n0 + (tid >> 1) : N - 1;
+  }
   const unsigned char* wg = w4 + wrow * (ldw >> 1) + (tid & 1) * 16;
 
   // this wave's tiles, and this lane's scale rows (one per n-tile)
@@ -174,11 +233,12 @@ __device__ __forceinline__ void kf_gq_body(
   const unsigned char* sg[2];
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const int64_t nt = n0 + wn * 64 + 32 * j;
+    const int64_t nt = n0 + wn * (SWIGLU ? 32 : 64) + (SWIGLU ? 0 : 32 * j);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
       live[j][i] = nt < N && m0 + wm * 64 + 32 * i < M;
     sg[j] = wscale + (nt + l31 < N ? nt + l31 : N - 1) * (ldw >> 5);
+    if (SWIGLU && j) sg[j] += N * (ldw >> 5);  // the up row
   }
   const int arow = wm * 64 + l31;
   const int wword = ((wn * 64 + l31) << 3) + hi * 4;
@@ -188,7 +248,7 @@ __device__ __forceinline__ void kf_gq_body(
 
   const int64_t npair = K / (2 * GQ_KS);
   kf_gq_stage st;
-  st.load(ag, lda, aok, wg, 0);
+  st.load<GATHER>(ag, lda, gidx, aok, wg, 0);
   unsigned int scn[2];
 #pragma unroll
   for (int j = 0; j < 2; ++j)
@@ -198,7 +258,7 @@ __device__ __forceinline__ void kf_gq_body(
   for (int64_t p = 0; p < npair; ++p) {
     const unsigned int sc[2] = {scn[0], scn[1]};
     // stage 2p in buffer 0; 2p + 1 exists (K % 128 == 0)
-    st.load(ag, lda, aok, wg, (2 * p + 1) * GQ_KS);
+    st.load<GATHER>(ag, lda, gidx, aok, wg, (2 * p + 1) * GQ_KS);
     // one barrier per stage: the buffer's writes are visible, and the readers
     // of the other buffer (the stage before) are done
     __syncthreads();
@@ -207,7 +267,7 @@ __device__ __forceinline__ void kf_gq_body(
     // stage 2p + 1 in buffer 1
     const bool more = p + 1 < npair;
     if (more) {
-      st.load(ag, lda, aok, wg, (2 * p + 2) * GQ_KS);
+      st.load<GATHER>(ag, lda, gidx, aok, wg, (2 * p + 2) * GQ_KS);
 #pragma unroll
       for (int j = 0; j < 2; ++j)
         scn[j] = *reinterpret_cast<const unsigned int*>(sg[j] + (p + 1) * 4);
@@ -219,6 +279,30 @@ __device__ __forceinline__ void kf_gq_body(
 
   // epilogue. C^T layout of the 32x32x16 MFMA: col = lane&31 is the C row,
   // row = (reg&3) + 8*(reg>>2) + 4*hi the C column: 4 consecutive n per quad
+  if (SWIGLU) {
+    // acc[0][i] is gate and acc[1][i] up of the same (row, column) per
+    // register: silu(g) * u in fp32 (kf_swiglu's expression), one rounding
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int64_t m = m0 + wm * 64 + 32 * i + l31;
+      if (!live[0][i] || m >= M) continue;
+      const int64_t at0 = m * ldc + n0 + wn * 32 + 4 * hi;
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq) {
+        float v[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const float g = acc[0][i][rq * 4 + t];
+          v[t] = g * (1.f / (1.f + __expf(-g))) * acc[1][i][rq * 4 + t];
+        }
+        unsigned int u[2] = {kf_cvt_pk_bf16_builtin(v[0], v[1]),
+                             kf_cvt_pk_bf16_builtin(v[2], v[3])};
+        *reinterpret_cast<kf_short4*>(c + at0 + 8 * rq) =
+            *reinterpret_cast<kf_short4*>(u);
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -246,6 +330,16 @@ __device__ __forceinline__ void kf_gq_body(
     }
 }
 
+template <bool GUARD, bool GATHER, bool SWIGLU>
+__device__ __forceinline__ void kf_gq_body(
+    const kf_gq_prob& pb, unsigned char (&a_lds)[2][GQ_A_TILEB],
+    unsigned char (&w_lds)[2][GQ_W_TILEB]) {
+  kf_gq_tile<GUARD, GATHER, SWIGLU>(pb.c, pb.a, pb.w4, pb.wscale, pb.res,
+                                    pb.M, pb.N, pb.K, pb.lda, pb.ldw, pb.ldc,
+                                    pb.tm, pb.tn, pb.a_rows, pb.a_nrows,
+                                    a_lds, w_lds);
+}
+
 __global__ __launch_bounds__(GQ_THREADS, 3) void kf_gemm_q4_kernel(
     unsigned short* __restrict__ c, const unsigned short* __restrict__ a,
     const unsigned char* __restrict__ w4,
@@ -256,12 +350,20 @@ __global__ __launch_bounds__(GQ_THREADS, 3) void kf_gemm_q4_kernel(
   __shared__ __attribute__((aligned(16))) unsigned char w_lds[2][GQ_W_TILEB];
   const bool full = ((int64_t)blockIdx.x + 1) * GQ_BM <= M &&
                     ((int64_t)blockIdx.y + 1) * GQ_BN <= N;
+  // the problem is built inside each branch, and the body multiplies the tile
+  // coordinates out itself: that is where the body computed its tile origin
+  // when it read blockIdx, and this kernel's instruction stream is, line for
+  // line, the one it had then (one kf_gq_prob in front of the branch is not)
+#define KF_GQ_PLAIN_PROB                                                 \
+  kf_gq_prob {                                                           \
+    c, a, w4, wscale, res, nullptr, 0, M, N, K, lda, ldw, ldc,           \
+        (int64_t)blockIdx.x, (int64_t)blockIdx.y                         \
+  }
   if (full)
-    kf_gq_body<false>(c, a, w4, wscale, res, M, N, K, lda, ldw, ldc, a_lds,
-                      w_lds);
+    kf_gq_body<false, false, false>(KF_GQ_PLAIN_PROB, a_lds, w_lds);
   else
-    kf_gq_body<true>(c, a, w4, wscale, res, M, N, K, lda, ldw, ldc, a_lds,
-                     w_lds);
+    kf_gq_body<true, false, false>(KF_GQ_PLAIN_PROB, a_lds, w_lds);
+#undef KF_GQ_PLAIN_PROB
 }
 
 // w4 [N, ldw / 2] bytes, wscale [N, ldw / 32] e8m0 bytes; ldw in fp4
@@ -289,5 +391,138 @@ KF_EXPORT int kf_gemm_q4(void* c, const void* a, const void* w4,
                      (const unsigned short*)a, (const unsigned char*)w4,
                      wscale, (const unsigned short*)res, M, N, K, lda, ldw,
                      ldc);
+  return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------
+// Grouped form for routed MoE prefill and verify steps: one launch runs every
+// expert's wide GEMM over the permuted [total_rows, .] buffer,
+//   lo = offsets[e], m = offsets[e+1] - lo
+//   c[lo + i, :] = a[a_rows ? a_rows[lo + i] : lo + i, :] @ dq(bank[e])^T
+// (swiglu: silu(gate) * up of the w13 bank's [2f, K] slices, c [., f]) on the
+// bank layout of kf_skinny_gemm_grouped_q4, with the body above: the k order
+// is kf_gemm_q4's wherever a tile starts, so with swiglu = 0 an expert's rows
+// are the bits kf_gemm_q4 gives for the same rows and bank slice.
+//
+// Tile map without a host sync. How many 128-row tiles an expert needs is
+// known only on the device, so the grid is (mt_bound, N tiles) with
+//   mt_bound = total_rows / 128 + min(E, total_rows)
+//           >= sum_e ceil(m_e / 128)   (each non-empty expert adds at most one
+//                                       partial tile, and there are at most
+//                                       min(E, total_rows) of those)
+// and M tiles fastest, so the blocks that share a weight tile are adjacent in
+// launch order as in the plain kernel. Every block finds its tile in registers
+// (E <= 64, one lane per expert): lane e loads and clamps its two offsets and
+// takes ceil(m_e / 128); an inclusive wave prefix sum and a ballot of
+// "prefix > blockIdx.x" give the expert as the first set bit, and readlane
+// its lo, m and first tile, all scalars. Each wave computes the same values,
+// so the result is block-uniform with no LDS and no barrier, and a block past
+// the last tile returns before any load of A or W.
+//
+// Memory safety, not validation (as the grouped skinny kernels): lo is
+// clamped into [0, total_rows], m into [0, total_rows - lo] and every a_rows
+// entry into [0, a_nrows), so no content of offsets or a_rows can cause an
+// out-of-range access; wrong offsets give wrong rows.
+
+struct kf_gq_group {
+  int e, lo, m, mt;  // expert, its first row and row count, the local tile
+};
+
+__device__ __forceinline__ bool kf_gq_find_tile(
+    const int* __restrict__ offsets, int n_experts, int total_rows, int tile,
+    kf_gq_group& g) {
+  const int lane = threadIdx.x & 63;
+  int lo = 0, m = 0;
+  if (lane < n_experts) {
+    const int o0 = offsets[lane];
+    // 64-bit difference: it cannot wrap for garbage offsets
+    const int64_t d = (int64_t)offsets[lane + 1] - o0;
+    lo = o0 < 0 ? 0 : (o0 > total_rows ? total_rows : o0);
+    m = d < 0 ? 0 : (d > total_rows - lo ? total_rows - lo : (int)d);
+  }
+  const int nt = (m + GQ_BM - 1) / GQ_BM;
+  int incl = nt;  // <= 64 * (2^31 / 128): no overflow
+#pragma unroll
+  for (int off = 1; off < KF_WAVE; off <<= 1) {
+    const int o = __shfl_up(incl, off, KF_WAVE);
+    if (lane >= off) incl += o;
+  }
+  const unsigned long long hit = __ballot(incl > tile);
+  if (hit == 0) return false;
+  const int e = __builtin_amdgcn_readfirstlane(__builtin_ctzll(hit));
+  g.e = e;
+  g.lo = __builtin_amdgcn_readlane(lo, e);
+  g.m = __builtin_amdgcn_readlane(m, e);
+  g.mt = tile - (__builtin_amdgcn_readlane(incl, e) -
+                 __builtin_amdgcn_readlane(nt, e));
+  return true;
+}
+
+// N: output columns (swiglu: f, the bank slice has 2 N rows)
+template <bool GATHER, bool SWIGLU>
+__global__ __launch_bounds__(GQ_THREADS, 3) void kf_gemm_q4_grouped_kernel(
+    unsigned short* __restrict__ c, const unsigned short* __restrict__ a,
+    const unsigned char* __restrict__ w4,
+    const unsigned char* __restrict__ wscale,
+    const int* __restrict__ offsets, const int* __restrict__ a_rows,
+    int n_experts, int total_rows, int a_nrows, int64_t N, int64_t K) {
+  __shared__ __attribute__((aligned(16))) unsigned char a_lds[2][GQ_A_TILEB];
+  __shared__ __attribute__((aligned(16))) unsigned char w_lds[2][GQ_W_TILEB];
+  kf_gq_group g;
+  if (!kf_gq_find_tile(offsets, n_experts, total_rows, (int)blockIdx.x, g))
+    return;
+  constexpr int BN = SWIGLU ? GQ_BN / 2 : GQ_BN;
+  const int64_t wrows = (int64_t)g.e * (SWIGLU ? 2 * N : N);
+  const kf_gq_prob pb{c + (int64_t)g.lo * N,
+                      GATHER ? a : a + (int64_t)g.lo * K,
+                      w4 + wrows * (K >> 1),
+                      wscale + wrows * (K >> 5),
+                      nullptr,
+                      GATHER ? a_rows + g.lo : nullptr,
+                      a_nrows,
+                      g.m, N, K, K, K, N,
+                      g.mt, (int64_t)blockIdx.y};
+  const bool full = (g.mt + 1) * GQ_BM <= g.m &&
+                    ((int64_t)blockIdx.y + 1) * BN <= N;
+  if (full)
+    kf_gq_body<false, GATHER, SWIGLU>(pb, a_lds, w_lds);
+  else
+    kf_gq_body<true, GATHER, SWIGLU>(pb, a_lds, w_lds);
+}
+
+// c [total_rows, swiglu ? N / 2 : N], a [a_nrows, K] (a_rows null: a_nrows >=
+// total_rows), all contiguous bf16; w4 [n_experts * N, K / 2], wscale
+// [n_experts * N, K / 32]; offsets int32 [n_experts + 1], a_rows nullable
+// int32 [total_rows], both device arrays. K % 128 == 0, N % 32 == 0 (swiglu:
+// N % 64 == 0), n_experts <= 64.
+KF_EXPORT int kf_gemm_q4_grouped(void* c, const void* a, const void* w4,
+                                 const unsigned char* wscale,
+                                 const int* offsets, const int* a_rows,
+                                 int64_t n_experts, int64_t total_rows,
+                                 int64_t a_nrows, int64_t N, int64_t K,
+                                 int swiglu, void* stream) {
+  if (n_experts < 1 || n_experts > 64 || total_rows < 0 ||
+      total_rows > INT32_MAX - GQ_BM || a_nrows < 1 || a_nrows >= INT32_MAX ||
+      K < 128 || K % 128 || N < 32 || N % 32 || (swiglu && N % 64) ||
+      N / (GQ_BN / 2) >= 65535 || (!a_rows && a_nrows < total_rows) ||
+      !offsets || (uintptr_t)a % 16 || (uintptr_t)w4 % 16 ||
+      (uintptr_t)wscale % 4 || (uintptr_t)c % 8)
+    return (int)hipErrorInvalidValue;
+  if (total_rows == 0) return 0;
+  const int64_t n_out = swiglu ? N / 2 : N;
+  const int64_t bn = swiglu ? GQ_BN / 2 : GQ_BN;
+  const int64_t mt_bound =
+      total_rows / GQ_BM + (n_experts < total_rows ? n_experts : total_rows);
+  dim3 grid((unsigned)mt_bound, (unsigned)((n_out + bn - 1) / bn), 1);
+#define KF_GQG_LAUNCH(GATHER, SWIGLU)                                         \
+  hipLaunchKernelGGL((kf_gemm_q4_grouped_kernel<GATHER, SWIGLU>), grid,       \
+                     dim3(GQ_THREADS), 0, (hipStream_t)stream,                \
+                     (unsigned short*)c, (const unsigned short*)a,            \
+                     (const unsigned char*)w4, wscale, offsets, a_rows,       \
+                     (int)n_experts, (int)total_rows, (int)a_nrows, n_out, K)
+  if (a_rows && swiglu) KF_GQG_LAUNCH(true, true);
+  else if (a_rows) KF_GQG_LAUNCH(true, false);
+  else if (swiglu) KF_GQG_LAUNCH(false, true);
+  else KF_GQG_LAUNCH(false, false);
   return (int)hipGetLastError();
 }

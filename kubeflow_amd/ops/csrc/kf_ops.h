@@ -97,6 +97,13 @@ KF_EXPORT int kf_skinny_gemm_grouped_q4(void* c, const void* a,
     const void* w4, const unsigned char* wscale, const int* offsets,
     const int* a_rows, int64_t n_groups, int64_t max_rows,
     int64_t total_rows, int64_t a_nrows, int64_t N, int64_t K, void* stream);
+// gemm_q4.hip, grouped: the same groups for any row count (routed MoE prefill
+// and verify steps), 128-row tiles found from the device offsets; swiglu: the
+// bank is w13 [n_experts * N, K], N = 2f, and c is silu(gate) * up, [., f]
+KF_EXPORT int kf_gemm_q4_grouped(void* c, const void* a, const void* w4,
+    const unsigned char* wscale, const int* offsets, const int* a_rows,
+    int64_t n_experts, int64_t total_rows, int64_t a_nrows, int64_t N,
+    int64_t K, int swiglu, void* stream);
 KF_EXPORT int kf_kv_store(void* ck, void* cv, const void* k, const void* v,
     const void* slots, const void* positions, int64_t smax, int64_t row,
     int64_t n, void* stream);

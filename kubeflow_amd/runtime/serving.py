@@ -252,7 +252,11 @@ class InferenceEngine:
         # KF_SERVE_QUANT_PREFILL=1 (with mxfp4): prefill runs wqkv, wo, w13
         # and w2 through ops.linear_q4 (kf_gemm_q4) on the same MXFP4 pairs
         # as decode, and the bf16 storage of those weights is released: the
-        # model is served from the 4-bit copy alone. Off by default.
+        # model is served from the 4-bit copy alone. An MoE model's experts
+        # then prefill through MoEMLP.prefill_routed (kf_gemm_q4_grouped) on
+        # the MXFP4 banks, and the bf16 banks are released too; it is refused
+        # where that kernel or the routed q4 decode cannot serve its shapes.
+        # Off by default.
         if quant_prefill is None:
             quant_prefill = os.environ.get("KF_SERVE_QUANT_PREFILL",
                                            "0") != "0"
@@ -261,10 +265,14 @@ class InferenceEngine:
             missing = {"qkv", "wo", "w13", "w2"} - skinny_selection()
             why = (f"it needs quant='mxfp4', got {quant!r}"
                    if quant != "mxfp4" else
-                   f"{cfg.name} is an MoE model, whose experts prefill "
-                   "through their bf16 banks" if moe else
                    f"KF_SKINNY leaves {sorted(missing)} of the decode step on "
-                   "the bf16 weights it would release" if missing else None)
+                   "the bf16 weights it would release" if missing else
+                   f"the experts of {cfg.name} need the routed MXFP4 kernels "
+                   "(a GPU, KF_MOE_DECODE=routed, max_batch <= 32, hidden and "
+                   "ffn sizes that are multiples of 1024), without which they "
+                   "run on the bf16 banks it would release"
+                   if moe and not (self._moe_quant_usable(max_batch)
+                                   and self._moe_prefill_q4_ok()) else None)
             if why:
                 raise ValueError(f"quant_prefill: {why}")
         if self.quant and moe and not self._moe_quant_usable(max_batch):
@@ -294,11 +302,18 @@ class InferenceEngine:
         if self.quant_prefill:
             # nothing reads these four any more: _decode_forward takes the
             # pairs (the KF_SKINNY check above) and prefill _prefill_linear
+            # (an MoE layer has no w13 / w2 but the two expert banks, which
+            # decode_routed and _prefill_mlp read as qw["moe"]; the gate stays)
+            def release(holder, name):
+                setattr(holder, name, torch.nn.Parameter(
+                    getattr(holder, name).new_empty(0), requires_grad=False))
             for layer in self.model.layers:
-                for n in ("wqkv", "wo", "w13", "w2"):
-                    w = getattr(layer, n).weight
-                    getattr(layer, n).weight = torch.nn.Parameter(
-                        w.new_empty(0), requires_grad=False)
+                for n in ("wqkv", "wo") if moe else ("wqkv", "wo", "w13",
+                                                     "w2"):
+                    release(getattr(layer, n), "weight")
+                if moe:
+                    release(layer.moe, "experts_w13")
+                    release(layer.moe, "experts_w2")
         # resident weight bytes: the model's parameters and the quantized
         # copies next to them
         self.weight_bytes = sum(
@@ -366,6 +381,15 @@ class InferenceEngine:
                             dtype=self.model.embed.weight.dtype)
         q4 = self.quant_format == "mxfp4"
         return all(layer.moe.routed_decode_ok(probe, q8=not q4, q4=q4)
+                   for layer in self.model.layers)
+
+    def _moe_prefill_q4_ok(self) -> bool:
+        """Every MoE layer's prefill (and its verify steps of more than 32
+        rows) can run from the MXFP4 banks: MoEMLP.routed_q4_ok."""
+        probe = torch.empty(1, 1, self.model.cfg.hidden_size,
+                            device=self.device,
+                            dtype=self.model.embed.weight.dtype)
+        return all(layer.moe.routed_q4_ok(probe)
                    for layer in self.model.layers)
 
     # ------------------------------------------------------------- public
@@ -914,6 +938,9 @@ class InferenceEngine:
     def _prefill_mlp(self, li, layer, x):
         """x + the layer's MLP block, shared by the three prefill paths."""
         if layer.moe is not None:  # MoE predictor (dense experts, EP=1)
+            if self.quant_prefill:  # the bf16 banks are released
+                return x + layer.moe.prefill_routed(layer.mlp_norm(x),
+                                                    self._qw[li]["moe"])
             return x + layer.moe(layer.mlp_norm(x))
         cfg = self.model.cfg
         g, u = self._prefill_linear(li, layer, "w13", layer.mlp_norm(x)).split(
